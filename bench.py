@@ -9,9 +9,9 @@ compaction, subframe decode (Rice, LPC rollback, decorrelation, PCM pack-out) an
 verification, inputs already in HBM, outputs left in HBM. Four runs are kept in flight
 (--inflight 4, each with its own buffers; bench.py sets ZFLAC_RUN_STREAMS to --inflight so
 each run has a run stream of its own), so one run's scan and walk overlap another's decode;
-`ms_per_step_serial` is the same shard one run at a time; that serial leg runs before the
-warm-up and the timed steps (the device ramps its clock up from idle over ~10-20 ms of load;
-`pre_timed_runs` in the JSON line) and gives the isolated kernel times from its second half.
+`--steps` runs of the same shard one at a time come before the warm-up and the timed steps
+(the device ramps its clock up from idle over ~10-20 ms of load; `pre_timed_runs` in the
+JSON line).
 N GPUs = N ranks with disjoint shards (weak
 scaling, no collective in the data path; torch.distributed only for the timing barrier
 and the max over ranks).
@@ -20,6 +20,13 @@ and the max over ranks).
 ranks itself (one child process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set
 before any HIP call); under torchrun WORLD_SIZE must equal --gpus. `--dry-run` runs the
 launcher, sharding and aggregation on CPU over gloo without touching a GPU (tests).
+
+A plain run does only that: it generates the shard, runs the pre-timed runs and the warm-up,
+times the steps, writes the last step's outputs if `--dump-outputs DIR` is given, and prints
+the result line (the legs below are null in it). Everything else is behind `--full`:
+
+`ms_per_step_serial`, the isolated kernel times and the roofline: with `--full` the pre-timed
+runs are a serial leg with HIP timing events, whose second half gives them.
 
 Bit-exactness gate: every stream of every in-flight batch is compared with the oracle's
 decode of it, and every stream's PCM hashes to its STREAMINFO MD5.
@@ -53,6 +60,7 @@ STREAMS_PER_GPU = 1250
 FRAMES_PER_STREAM = 32
 BLOCK = 4096
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md, HBM3E peak
+DUMP_SAMPLE_BYTES = 48 << 20  # --dump-outputs: float32 PCM of the sampled streams (48 of the C5 shard's)
 METRIC = "Msamples/s decoded (bit-exact) + achieved HBM GB/s, 4096-blk stereo"
 # PMC summary of the current k_decode build (tools/gpu.sh pmc; FETCH_SIZE /
 # WRITE_SIZE corrected by the factors tools/calib_pmc.hip measures for this access pattern)
@@ -99,6 +107,13 @@ def parse_args():
     ap.add_argument("--inflight", type=int, default=4,
                     help="shard runs overlapped on the device (1 = serial), on as many run streams")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: the serial leg (isolated kernel times, roofline), "
+                         "the oracle comparison of every stream, the decode+MD5 leg, the CPU baseline and the "
+                         "end-to-end decode() legs (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left to DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--streams-per-gpu", type=int, default=STREAMS_PER_GPU)
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline sample budget (all cores)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -273,6 +288,61 @@ def verify(batches, streams):
     for t in ts:
         t.join()
     return errs, sum(compared)
+
+
+def run_totals(batch):
+    """The library's zflac_timings of the batch's last run. Its samples / input_bytes /
+    output_bytes are filled whether or not the batch records HIP events (Batch.timings() is
+    None for one that does not)."""
+    import ctypes
+
+    from zflac_amd import _lib
+
+    t = _lib.zflac_timings()
+    _lib.load().zflac_hip_batch_timings_ex(batch._h, ctypes.byref(t), ctypes.sizeof(t))
+    return t
+
+
+def dump_outputs(batch, out_dir: str, rank: int) -> None:
+    """What the last timed run left in `batch`, as a caller gets it from zflac_hip_batch_info /
+    _read, written as .npy files (the shard is seeded, so two builds given the same arguments
+    can be compared file for file):
+      stream_sums.npy     float64 [streams, 4]: status, sample count, sum of the samples, and
+                          sum of sample k x (k mod 65521 + 1) mod 2^32, for every stream
+      samples.npy         float32: the interleaved PCM of a fixed seeded choice of streams, one
+                          after the other (DUMP_SAMPLE_BYTES at the most; the whole shard is ~1.3 GB)
+      sample_streams.npy  float64 [chosen, 2]: stream index and sample count of each of those
+    Ranks other than 0 append _rank<r> to the names."""
+    n = len(batch)
+    infos = [batch.info(i) for i in range(n)]
+    chosen, used = [], 0
+    for i in np.random.default_rng(0).permutation(n):
+        nb = 0 if infos[i][0] else infos[i][1].samples_bytes // (1, 2, 4)[infos[i][1].sample_kind] * 4
+        if used + nb > DUMP_SAMPLE_BYTES:
+            break
+        chosen.append(int(i))
+        used += nb
+    sums = np.zeros((n, 4), dtype=np.float64)
+    kept = {}
+    weights = {}
+    for i, (rc, _) in enumerate(infos):
+        sums[i, 0] = rc
+        if rc:
+            continue
+        x = batch.read(i, verify_md5=False).samples.values
+        if i in chosen:
+            kept[i] = x.astype(np.float32)
+        x = x.astype(np.int64)
+        if x.size not in weights:
+            weights[x.size] = np.arange(x.size, dtype=np.int64) % 65521 + 1
+        sums[i, 1:] = x.size, int(x.sum()), int((x * weights[x.size]).sum()) & 0xFFFFFFFF
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(out_dir, f"stream_sums{tag}.npy"), sums)
+    np.save(os.path.join(out_dir, f"samples{tag}.npy"),
+            np.concatenate([kept[i] for i in chosen if i in kept] or [np.zeros(0, np.float32)]))
+    np.save(os.path.join(out_dir, f"sample_streams{tag}.npy"),
+            np.array([[i, kept[i].size] for i in chosen if i in kept], dtype=np.float64).reshape(-1, 2))
 
 
 def e2e_leg(name: str, cfg: dict, seg_frames: int, frames: int, oracle_full: bool):
@@ -470,7 +540,7 @@ def main():
     backend = args.backend or ("gloo" if (args.dry_run or args.same_device) else "nccl")
     # the decode+MD5 leg (reported for rank 0 only) runs on rank 0 alone: at world 8 that is 9
     # processes on the node instead of 16, the other ranks' GPUs idle meanwhile
-    md5_proc = None if (args.no_md5 or rank != 0) else start_md5_child(args)
+    md5_proc = start_md5_child(args) if (args.full and not args.no_md5 and rank == 0) else None
     # one run stream per run in flight (read by the library when it first uses the device;
     # the HIP default of four hardware queues covers four run streams)
     os.environ.setdefault("ZFLAC_RUN_STREAMS", str(max(1, args.inflight)))
@@ -541,8 +611,10 @@ def main():
     n_inf = max(1, min(args.inflight, args.steps))  # every batch runs (and is verified)
     timed_ev = args.timed_events == "on" or n_inf == 1  # (one in flight: no serial leg, the timed runs give the times)
     batches = [zflac_amd.Batch(streams, device=device, timing=timed_ev) for _ in range(n_inf)]
-    # the serial leg's batch always records its stage events (the isolated kernel times)
-    serial_batch = batches[:1] if timed_ev else [zflac_amd.Batch(streams, device=device, timing=True)]
+    # the serial leg's batch (--full) always records its stage events (the isolated kernel times);
+    # a plain run's pre-timed runs use the first timed batch
+    serial_batch = (batches[:1] if (timed_ev or not args.full)
+                    else [zflac_amd.Batch(streams, device=device, timing=True)])
     STAGES = ("scan_ms", "walk_ms", "decode_ms", "verify_ms")
 
     def run_steps(k, bs, rec=None):
@@ -584,16 +656,20 @@ def main():
     # runs, 0.47-0.49 once the device has been busy ~20 ms, 0.55-0.57 after a 50-500 ms
     # idle gap). The isolated times come from the leg's second half, where the clock has
     # settled (and `ms_per_step_serial` from the same half). The timed steps are unchanged:
-    # `warmup` runs, a barrier, `steps` runs.
+    # `warmup` runs, a barrier, `steps` runs. A plain run keeps the same `steps` pre-timed
+    # runs, so its timed steps start from the same clock, but measures nothing in them.
     serial = None
     rec = None
     if n_inf > 1:
         half = args.steps // 2
         run_steps(half, serial_batch)
-        rec = {n: [] for n in STAGES}
-        t1 = time.perf_counter()
-        run_steps(args.steps - half, serial_batch, rec)
-        serial = (time.perf_counter() - t1) / (args.steps - half)
+        if args.full:
+            rec = {n: [] for n in STAGES}
+            t1 = time.perf_counter()
+            run_steps(args.steps - half, serial_batch, rec)
+            serial = (time.perf_counter() - t1) / (args.steps - half)
+        else:
+            run_steps(args.steps - half, serial_batch)
     run_steps(args.warmup, batches)
     progress("warm-up done")
     barrier_sync()
@@ -602,7 +678,7 @@ def main():
     run_steps(args.steps, batches, rec_ov if timed_ev else None)
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    tm = batches[0].timings() or serial_batch[0].timings()
+    tm = run_totals(batches[0])
     samples_rank = tm.samples
     in_bytes, out_bytes = tm.input_bytes, tm.output_bytes
     if rec is None:
@@ -610,9 +686,14 @@ def main():
     scan_ms, walk_ms, dec_ms, ver_ms = (rec[n] for n in STAGES)
 
     progress(f"timed steps done ({elapsed / args.steps * 1e3:.3f} ms/step)")
+    if args.dump_outputs:
+        # the batch of the last timed step (round robin; under --sched ready every batch has
+        # run the same shard, so any of them holds what the last step computed)
+        dump_outputs(batches[(args.steps - 1) % n_inf], args.dump_outputs, rank)
+        progress(f"outputs written to {args.dump_outputs}")
     errs = []
     n_compared = 0
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         errs, n_compared = verify(batches, streams)
     for b in batches[1:]:
         b.close()
@@ -637,7 +718,7 @@ def main():
 
     cpu = None
     e2e = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             progress("CPU baseline")
             cpu = cpu_baseline(streams, args.cpu_seconds)
@@ -652,13 +733,26 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = samples_all * args.steps / elapsed / 1e6
-        dec_avg = float(np.mean(dec_ms))
-        alg_bytes = in_bytes + out_bytes  # per decode launch (this rank)
-        achieved = alg_bytes / (dec_avg * 1e-3) / 1e9
         lib_sha = hashlib.sha256(open(zflac_amd.lib_path, "rb").read()).hexdigest()
         bid = zflac_amd.build_id()  # embedded by the build: the sources of the loaded library
         src_sha = bid[4:] if bid and bid.startswith("src=") else None
-        pmc = pmc_traffic("zflac::k_decode<1, 2", lib_sha, src_sha)
+        # stage times exist where HIP events were recorded: the serial leg (--full), or the timed
+        # steps themselves (--timed-events on, or one run in flight)
+        roofline = stages = pmc = None
+        if dec_ms:
+            dec_avg = float(np.mean(dec_ms))
+            alg_bytes = in_bytes + out_bytes  # per decode launch (this rank)
+            achieved = alg_bytes / (dec_avg * 1e-3) / 1e9
+            pmc = pmc_traffic("zflac::k_decode<1, 2", lib_sha, src_sha)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc["bytes"] if pmc else None,
+                        "kernel": "k_decode<1, 2, *> (order-bucket launches, one event pair)",
+                        "kernel_ms": round(dec_avg, 4),
+                        "kernel_timing": "isolated launches (serial leg, one run in flight)" if serial else "timed steps",
+                        "alg_bytes_per_launch": int(alg_bytes)}
+            stages = {"scan+compact": round(float(np.mean(scan_ms)), 4),
+                      "walk": round(float(np.mean(walk_ms)), 4), "decode": round(dec_avg, 4),
+                      "verify": round(float(np.mean(ver_ms)), 4)}
         line = {
             "metric": METRIC,
             "value": round(value, 1),
@@ -669,9 +763,10 @@ def main():
             "ms_per_step": round(ms_step, 4),
             "inflight": n_inf,
             "ms_per_step_serial": round(serial * 1e3, 4) if serial else None,
-            "pre_timed_runs": {"serial_leg": args.steps if serial else 0, "warmup": args.warmup,
-                               "why": "the serial leg (one run at a time, isolated kernel times) runs before the "
-                                      "warm-up: the device leaves idle at a lower clock (profiles/r5_warm_test.json)"},
+            "pre_timed_runs": {"serial_leg": args.steps if n_inf > 1 else 0, "warmup": args.warmup,
+                               "why": "the serial leg (one run at a time; with --full, the isolated kernel times) "
+                                      "runs before the warm-up: the device leaves idle at a lower clock "
+                                      "(profiles/r5_warm_test.json)"},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -682,16 +777,11 @@ def main():
                                                                        BLOCK),
                        "streams_total": args.streams_per_gpu * world, "parallelism": f"stream-shard x{world}"},
             "hbm_gbs_step": round((in_all + out_all) * args.steps / elapsed / 1e9, 1),
-            "bit_exact": ok,
+            "full": args.full,
+            "bit_exact": ok if args.full else None,  # a plain run compares nothing
             "oracle_compared": f"{n_compared}/{len(streams)} streams x {len(batches)} in-flight batches (rank 0)",
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc["bytes"] if pmc else None,
-                         "kernel": "k_decode<1, 2, *> (order-bucket launches, one event pair)", "kernel_ms": round(dec_avg, 4),
-                         "kernel_timing": "isolated launches (serial leg, one run in flight)" if serial else "timed steps",
-                         "alg_bytes_per_launch": int(alg_bytes)},
-            "stages_ms": {"scan+compact": round(float(np.mean(scan_ms)), 4),
-                          "walk": round(float(np.mean(walk_ms)), 4), "decode": round(dec_avg, 4),
-                          "verify": round(float(np.mean(ver_ms)), 4)},
+            "roofline": roofline,
+            "stages_ms": stages,
             "stages_ms_overlapped": {"scan+compact": round(float(np.mean(rec_ov["scan_ms"])), 4),
                                      "walk": round(float(np.mean(rec_ov["walk_ms"])), 4),
                                      "decode": round(float(np.mean(rec_ov["decode_ms"])), 4)}

@@ -137,7 +137,8 @@ def test_bench_self_launch_dry_run_world8():
     ranks; rank 0 also starts its decode+MD5 child (the leg is reported for rank 0 only), which
     receives the rank's shard over a pipe (it does not regenerate it); host threads are the
     job's cores split over the ranks."""
-    d = _bench("--gpus", "8", "--dry-run", "--streams-per-gpu", "2", "--steps", "1", "--warmup", "0", timeout=600)
+    d = _bench("--gpus", "8", "--dry-run", "--full", "--streams-per-gpu", "2", "--steps", "1", "--warmup", "0",
+               timeout=600)
     assert d["n_gpus"] == 8 and len(d["ranks"]) == 8
     assert d["shards"] == [[2 * r, 2 * r + 2] for r in range(8)]
     assert d["ranks"][0]["child_got_shard"] and d["ranks"][0]["processes"] == 2
@@ -165,6 +166,37 @@ def test_bench_two_ranks_two_hip_contexts(gpu_ready):
     only GPU of the test box), gloo for the barrier: shards decode bit-exactly and the
     job line covers both ranks."""
     d = _bench("--gpus", "2", "--same-device", "--streams-per-gpu", "16", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-md5", "--no-e2e")
+               "--full", "--no-cpu-baseline", "--no-md5", "--no-e2e")
     assert d["n_gpus"] == 2 and d["bit_exact"] is True
     assert d["config"]["streams_total"] == 32 and d["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(gpu_ready, tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the legs beside the headline
+    are null in its line. `--dump-outputs` writes what the last timed step decoded: every
+    stream's status, count and sums, and the PCM of the sampled streams (here all 6), equal to
+    what the generator encoded."""
+    import numpy as np
+    import synth
+
+    import bench
+
+    d = _bench("--gpus", "1", "--streams-per-gpu", "6", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "int32"
+    for leg in ("device_md5", "cpu_baseline", "e2e_decode", "ms_per_step_serial", "roofline", "bit_exact"):
+        assert d[leg] is None, leg
+    sums = np.load(tmp_path / "stream_sums.npy")
+    pcm = np.load(tmp_path / "samples.npy")
+    which = np.load(tmp_path / "sample_streams.npy")
+    assert sums.dtype == np.float64 and pcm.dtype == np.float32 and sums.shape == (6, 4)
+    assert sorted(which[:, 0]) == list(range(6))
+    off = 0
+    for i, n in which.astype(np.int64):
+        ref = synth.generate(**synth.config_c5(int(i), n_frames=bench.FRAMES_PER_STREAM)).pcm.reshape(-1)
+        assert n == ref.size and np.array_equal(pcm[off:off + n], ref.astype(np.float32)), f"stream {i}"
+        assert sums[i, 0] == 0 and sums[i, 1] == n and sums[i, 2] == int(ref.astype(np.int64).sum())
+        off += n
+    assert off == pcm.size

@@ -6,5 +6,6 @@ python -c "import json;d=json.loads(open('gpurun_out/$T/bench.json').read().stri
 bash tools/gpu.sh pmc $T || { tail -20 gpurun_out/$T/pmc_summary.log; exit 1; }
 tail -5 gpurun_out/$T/pmc_summary.log
 bash tools/gpu.sh profile $T || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > gpurun_out/$T/bench20.json 2> gpurun_out/$T/bench20.err || exit 1
-python -c "import json;d=json.loads(open('gpurun_out/$T/bench20.json').read().strip().splitlines()[-1]);print('20 steps', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'])"
+O=$(dirname $(ls -t */$T/bench.json | head -1))  # where tools/gpu.sh check put its files
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench20.json 2> $O/bench20.err || exit 1
+python -c "import json;d=json.loads(open('$O/bench20.json').read().strip().splitlines()[-1]);print('20 steps', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic'])"

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 O=gpurun_out/$1; mkdir -p $O
 A=$2; B=$3; N=${4:-3}
-QUIET="--no-cpu-baseline --no-e2e --no-md5"
+QUIET="--full --no-cpu-baseline --no-e2e --no-md5"
 for i in $(seq 1 $N); do
   for v in A B; do
     L=$A; [ $v = B ] && L=$B

@@ -31,7 +31,7 @@ CMD=$1; TAG=$2; shift 2
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-QUIET="--no-cpu-baseline --no-e2e --no-md5"
+QUIET="--full --no-cpu-baseline --no-e2e --no-md5"
 
 prof() {  # prof <outdir> <cmd...>: rocprofv3 kernel statistics of one command
   local d=$1; shift
@@ -45,13 +45,13 @@ case $CMD in
         > $O/gputest.txt 2>&1
     ;;
   bench)
-    timeout -k 10 600 python bench.py "$@" > $O/bench.json 2> $O/bench.err
+    timeout -k 10 600 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err
     ;;
   check)
     timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
         > $O/gputest.txt 2>&1 || exit $?
     timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || exit $?
-    timeout -k 10 600 python bench.py "$@" > $O/bench.json 2> $O/bench.err
+    timeout -k 10 600 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err
     ;;
   profile)
     prof $O/serial python3 $R/bench.py --steps 20 --warmup 3 $QUIET --inflight 1 "$@" > $O/serial.log 2>&1 || exit $?

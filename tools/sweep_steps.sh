@@ -2,7 +2,7 @@
 # bench.py step-count / scheduling sweep on one box: sweep_steps.sh <tag> "<steps> <sched>"...
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 O=gpurun_out/$1; shift; mkdir -p $O
-QUIET="--no-cpu-baseline --no-e2e --no-md5"
+QUIET="--full --no-cpu-baseline --no-e2e --no-md5"
 for cfg in "$@"; do
   set -- $cfg
   n="s$1_$2"
