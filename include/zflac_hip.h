@@ -93,9 +93,15 @@ typedef struct zflac_timings {
      * history bucket the batch's launch plan had not predicted; the bucket is then added to
      * the plan, so a later run of the same batch has none */
     uint32_t rest_launches;
-    /* (ABI 5) streams of the last run finished by the sequential chain planner (the chain
-     * check did not certify them: false syncs, a broken frame, a wrong STREAMINFO, a total
-     * unknown without a minimum frame size); 0 when the parallel pass certified every one */
+    /* (ABI 5) streams of the last run finished by the sequential chain planner, because the
+     * parallel pass's chain check (k_verify) did not certify them: a stream that ends in an
+     * error (a broken or truncated frame, frames that disagree with STREAMINFO), candidates
+     * that do not form one chain up to the STREAMINFO total (false syncs the check could not
+     * rule out, missing or extra frames), or a batch created with ZFLAC_FLAG_FORCE_SLOW. A
+     * stream whose STREAMINFO total is unknown is certified by the parallel pass like any
+     * other; it reaches the planner only through a broken chain, bytes after its last frame,
+     * or an output reservation dropped at creation (a flood of false syncs, the memory cap).
+     * 0 when the parallel pass certified every stream */
     uint32_t sequential_streams;
 } zflac_timings;
 
@@ -172,6 +178,43 @@ int zflac_hip_batch_timings_ex(zflac_batch *b, zflac_timings *t, size_t size);
 size_t zflac_hip_batch_size(zflac_batch *b);
 void zflac_hip_batch_destroy(zflac_batch *b);
 
+/* ---- dense device export --------------------------------------------------------- */
+/* The batch's decoded samples as one dense tensor in caller-owned device memory, written by
+ * one HIP kernel (k_export): B rows (one per stream, in batch order) of `channels` x `frames`
+ * elements. Row i holds frames [starts[i], starts[i] + frames) of stream i. Frames at or
+ * past the stream's end and channels the stream does not have are zero; a stream with more
+ * than `channels` channels exports its first `channels`; a stream whose result is an error
+ * exports an all-zero row. Every element of the destination is written. */
+#define ZFLAC_EXPORT_F32 0  /* (float)sample * 2^-(container bits - 1): 2^-7, 2^-15 or 2^-31 (exact;
+                               the int->float conversion rounds 25..32-bit samples to nearest-even) */
+#define ZFLAC_EXPORT_F16 1  /* that f32 value rounded to nearest-even to IEEE half, subnormals kept */
+#define ZFLAC_EXPORT_BF16 2 /* that f32 value rounded to nearest-even to bfloat16 */
+#define ZFLAC_EXPORT_I32 3  /* the container value sign-extended (the number zflac_hip_batch_read returns) */
+#define ZFLAC_LAYOUT_PLANAR 0      /* [row][channel][frame] */
+#define ZFLAC_LAYOUT_INTERLEAVED 1 /* [row][frame][channel] */
+typedef struct zflac_export_desc {
+    uint32_t size;          /* sizeof(zflac_export_desc) */
+    uint8_t dtype, layout;  /* ZFLAC_EXPORT_*, ZFLAC_LAYOUT_* */
+    uint16_t channels;      /* C >= 1 */
+    uint64_t frames;        /* T >= 1 */
+    const uint64_t *starts; /* host array, one per stream, or NULL = all 0 */
+} zflac_export_desc;
+/* Export the last completed run. dst_device: B * C * T elements of the dtype on the batch's
+ * device (any alignment; 16-byte aligned rows take the fast paths). valid_frames (host, B
+ * entries, may be NULL) receives clamp(frames of stream i - starts[i], 0, T), 0 for an error
+ * stream. stream == NULL: runs on the batch's own stream and returns when the tensor is
+ * complete. Otherwise `stream` is a hipStream_t of the batch's device: the export is enqueued
+ * there and the call returns without synchronising, so later work on that stream sees the
+ * tensor; the batch's next run waits for it on the device, and _destroy on the host.
+ * ZFLAC_E_INVALID_ARGUMENT (nothing written): NULL batch / desc / dst, desc->size, an unknown
+ * dtype or layout, channels or frames of 0, dst_bytes < B*C*T*element size, before the first
+ * completed run, between _submit and _wait. ZFLAC_E_DEVICE on a HIP failure. */
+int zflac_hip_batch_export(zflac_batch *b, const zflac_export_desc *d, void *dst_device, size_t dst_bytes,
+                           uint64_t *valid_frames, void *stream);
+/* Device time of the last synchronous (stream == NULL) export of a batch created with
+ * ZFLAC_FLAG_TIMING (table copy + k_export); ZFLAC_E_INVALID_ARGUMENT when there is none. */
+int zflac_hip_batch_export_ms(zflac_batch *b, double *ms);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -208,7 +251,9 @@ const char *zflac_hip_build_id(void);
  * 3: zflac_hip_batch_timings_ex, zflac_hip_abi_version; device MD5 pipelined into submit.
  * 4: zflac_timings.rest_launches; zflac_hip_build_id; zflac_hip_batch_ready.
  * 5: zflac_timings.sequential_streams (was reserved0); total-unknown streams certified by the
- *    parallel pass. */
+ *    parallel pass.
+ *    Added without a bump (no existing struct or signature changed): zflac_export_desc,
+ *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Time the dense device export (k_export) on the C5 shard against the torch composition a
+user would otherwise write, in one process.
+
+    python tools/bench_export.py [--streams 1250] [--iters 50] [--warmup 5] [--out profiles/export_bench.json]
+
+The shard is bench.make_shard's (1,250 stereo 16-bit streams of 32 x 4,096 frames). It is decoded
+once; then every iteration times, with torch CUDA events on the export's stream, one export of
+each variant (planar f32, planar f16, interleaved f32) and one run of the comparator
+
+    x.to(torch.float32).mul_(2**-15).permute(0, 2, 1).contiguous()
+
+over the same samples held as one int16 [B, T, C] tensor (built once, outside the timed
+region). Reported per variant: min / median / max milliseconds and the fraction of the 8.0 TB/s
+HBM peak that (bytes read + bytes written, from the shapes) / time amounts to. Those intervals
+hold the host side of a call from Python as well (the device idles while the call is prepared), so
+each variant is also timed by the library's own HIP events around the table copy and the kernel
+("device", synchronous exports through the C call)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch  # before zflac_amd loads its library (zflac_amd/tensor.py)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+import zflac_amd  # noqa: E402
+from zflac_amd import tensor  # noqa: E402
+
+HBM_PEAK = 8.0e12  # bytes/s
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=bench.STREAMS_PER_GPU)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export_bench.json"))
+    a = ap.parse_args()
+    assert a.iters >= 50, "at least 50 timed exports per variant"
+
+    streams = bench.make_shard(0, 1, a.streams)
+    batch = zflac_amd.Batch(streams, timing=True)
+    batch.run()
+    batch.run()  # the second run has no first-run planning in it
+    tm = batch.timings()
+    B = len(batch)
+    assert all(batch.info(i)[0] == 0 for i in range(B))
+    C = 2
+    T = bench.FRAMES_PER_STREAM * 4096
+    side = torch.cuda.Stream()
+
+    variants = {
+        "planar_f32": dict(dtype=torch.float32, layout="planar"),
+        "planar_f16": dict(dtype=torch.float16, layout="planar"),
+        "interleaved_f32": dict(dtype=torch.float32, layout="interleaved"),
+    }
+    outs, nbytes = {}, {}
+    src_bytes = B * T * C * 2  # the 16-bit containers k_export reads
+    with torch.cuda.stream(side):
+        for name, kw in variants.items():
+            shape = (B, C, T) if kw["layout"] == "planar" else (B, T, C)
+            outs[name] = torch.empty(shape, dtype=kw["dtype"], device="cuda")
+            nbytes[name] = src_bytes + outs[name].numel() * outs[name].element_size()
+        # the comparator's input: the same samples as int16 [B, T, C]
+        x32, lengths = tensor.export(batch, frames=T, channels=C, dtype=torch.int32, layout="interleaved", stream=side)
+        x16 = x32.to(torch.int16)
+        del x32
+    side.synchronize()
+    assert lengths.cpu().tolist() == [T] * B
+    # to (r 2, w 4) + mul_ (r 4, w 4) + contiguous (r 4, w 4) bytes per element
+    nbytes["torch_composition"] = B * T * C * (2 + 4 + 4 + 4 + 4 + 4)
+
+    def comparator():
+        return x16.to(torch.float32).mul_(2 ** -15).permute(0, 2, 1).contiguous()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        r = fn()
+        e1.record(side)
+        side.synchronize()
+        return e0.elapsed_time(e1), r
+
+    times = {k: [] for k in list(variants) + ["torch_composition"]}
+    with torch.cuda.stream(side):
+        for it in range(a.warmup + a.iters):
+            for name, kw in variants.items():
+                ms, _ = timed(lambda: tensor.export(batch, frames=T, channels=C, out=outs[name], stream=side, **kw))
+                if it >= a.warmup:
+                    times[name].append(ms)
+            ms, y = timed(comparator)
+            if it >= a.warmup:
+                times["torch_composition"].append(ms)
+        same = bool(torch.equal(y, outs["planar_f32"]))
+        del y
+    assert same, "the export and the torch composition disagree"
+
+    # The device side alone: synchronous exports through the C call on the batch's own stream,
+    # timed by the library's HIP events around the table copy and k_export (ZFLAC_FLAG_TIMING).
+    import ctypes
+
+    from zflac_amd import _lib
+
+    codes = {torch.float32: _lib.EXPORT_F32, torch.float16: _lib.EXPORT_F16}
+    device_ms = {}
+    ms = ctypes.c_double()
+    for name, kw in variants.items():
+        d = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), codes[kw["dtype"]],
+                                   _lib.LAYOUT_PLANAR if kw["layout"] == "planar" else _lib.LAYOUT_INTERLEAVED, C, T, None)
+        o = outs[name]
+        ts = []
+        for it in range(a.warmup + a.iters):
+            rc = batch._L.zflac_hip_batch_export(batch._h, ctypes.byref(d), o.data_ptr(), o.numel() * o.element_size(),
+                                                 None, None)
+            assert rc == 0 and batch._L.zflac_hip_batch_export_ms(batch._h, ctypes.byref(ms)) == 0
+            if it >= a.warmup:
+                ts.append(ms.value)
+        device_ms[name] = ts
+
+    res = {"build_id": zflac_amd.build_id(), "device": torch.cuda.get_device_name(0), "streams": B, "channels": C,
+           "frames": T, "iters": a.iters, "warmup": a.warmup, "hbm_peak_bytes_per_s": HBM_PEAK,
+           "decode_step_ms": {"total": tm.total_ms, "scan": tm.scan_ms, "walk": tm.walk_ms, "decode": tm.decode_ms,
+                              "verify": tm.verify_ms} if tm is not None else None,
+           "export_equals_torch_composition": same, "variants": {}}
+    for name, ts in times.items():
+        med = statistics.median(ts)
+        res["variants"][name] = {"min_ms": min(ts), "median_ms": med, "max_ms": max(ts), "bytes": nbytes[name],
+                                 "hbm_fraction_at_median": nbytes[name] / (med * 1e-3) / HBM_PEAK}
+    for name, ts in device_ms.items():
+        med = statistics.median(ts)
+        res["variants"][name]["device"] = {"min_ms": min(ts), "median_ms": med, "max_ms": max(ts),
+                                           "hbm_fraction_at_median": nbytes[name] / (med * 1e-3) / HBM_PEAK}
+    v = res["variants"]
+    res["planar_f32_not_slower_than_torch"] = v["planar_f32"]["median_ms"] <= v["torch_composition"]["median_ms"]
+    batch.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0 if res["planar_f32_not_slower_than_torch"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -33,6 +33,11 @@ class zflac_timings(ctypes.Structure):
                 ("crc16_ms", ctypes.c_double), ("rest_launches", ctypes.c_uint32), ("sequential_streams", ctypes.c_uint32)]
 
 
+class zflac_export_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("channels", ctypes.c_uint16), ("frames", ctypes.c_uint64), ("starts", ctypes.POINTER(ctypes.c_uint64))]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -55,6 +60,9 @@ SIGNATURES = {
     "zflac_hip_batch_timings": (ctypes.c_int, [_P, ctypes.POINTER(zflac_timings)]),
     "zflac_hip_batch_timings_ex": (ctypes.c_int, [_P, ctypes.POINTER(zflac_timings), ctypes.c_size_t]),
     "zflac_hip_abi_version": (ctypes.c_int, []),
+    "zflac_hip_batch_export": (ctypes.c_int, [_P, ctypes.POINTER(zflac_export_desc), _P, ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_uint64), _P]),
+    "zflac_hip_batch_export_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "zflac_hip_batch_size": (ctypes.c_size_t, [_P]),
     "zflac_hip_batch_destroy": (None, [_P]),
     "zflac_hip_error_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -69,6 +77,13 @@ FLAG_DEVICE_MD5 = 4
 FLAG_CHECK_CRC16 = 8  # beyond zflac (src/zflac.zig:548-551 ignores the trailer)
 FLAG_WALK_LANE = 16
 FLAG_WALK_WAVE = 32
+# zflac_hip_batch_export: element type and layout of the dense tensor
+EXPORT_F32 = 0
+EXPORT_F16 = 1
+EXPORT_BF16 = 2
+EXPORT_I32 = 3
+LAYOUT_PLANAR = 0
+LAYOUT_INTERLEAVED = 1
 
 _lib = None
 

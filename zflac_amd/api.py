@@ -115,6 +115,7 @@ class Batch:
     def __init__(self, streams, device: int = 0, timing: bool = False, force_slow: bool = False,
                  device_md5: bool = False, check_crc16: bool = False, walk: str | None = None):
         self._L = _lib.load()
+        self.device = device
         self._bufs = [bytes(s) for s in streams]
         arr = (_lib.zflac_stream * len(self._bufs))()
         self._keep = []

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzflac_hip.so")
 SOURCES = [os.path.join(CSRC, f"decode_k{k}_{lay}{mix}.hip") for k in (1, 2, 0) for lay in ("stereo", "mono", "multi")
            for mix in ("", "_mix")]
-SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "host.cpp")]
+SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip", "host.cpp")]
 HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "md5.hpp", "device_common.h", "decode.inc")]
 DEPS = SOURCES + HEADERS + [os.path.join(ROOT, "include", "zflac_hip.h")]
 ARCH = os.environ.get("ZFLAC_OFFLOAD_ARCH", "gfx950")

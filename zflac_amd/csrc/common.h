@@ -243,4 +243,31 @@ struct Crc16Args {
     uint32_t* bad;             // per frame: 1 when the stored CRC-16 differs
 };
 
+// k_export (export.hip): one row of the dense destination. Row i takes frames
+// [start, start + T) of its stream; src == nullptr (an error stream, no frames, or a window
+// wholly past the end) makes the row all zero.
+struct ExportRow {
+    const void* src;    // the stream's decoded samples: interleaved, left-justified, container-typed
+    uint64_t n_frames;  // frames of the stream
+    uint64_t start;     // first frame of the window (< n_frames when src != nullptr)
+    uint8_t nch;        // channels of the stream
+    uint8_t kind;       // ZFLAC_S8 / ZFLAC_S16 / ZFLAC_S32 container
+    uint8_t pad_[6];
+};
+static_assert(sizeof(ExportRow) == 32, "ExportRow is the 32-byte record host and kernel share");
+
+constexpr uint32_t EXPORT_THREADS = 256;
+constexpr uint32_t EXPORT_GROUP = 16;  // frames (or flat elements) per lane
+constexpr uint64_t EXPORT_TILE = (uint64_t)EXPORT_THREADS * EXPORT_GROUP;  // frames of a row per workgroup
+
+struct ExportArgs {
+    const ExportRow* rows;
+    void* dst;             // B x C x T elements of the export's dtype
+    uint64_t frames;       // T
+    uint32_t channels;     // C
+    uint32_t n_rows;       // B
+    uint32_t tiles;        // tiles per row: ceil(T / EXPORT_TILE); grid = n_rows * tiles
+    uint32_t vec;          // dst and its rows are 16-byte aligned: the 16-byte store paths apply
+};
+
 }  // namespace zflac

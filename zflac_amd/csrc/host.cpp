@@ -103,6 +103,7 @@ hipError_t launch_sync_list(const SyncListArgs& a, hipStream_t st);
 // kernel), or -1 (lane-per-stream loads)
 hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode);
 hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode);
+hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st);
 
 namespace {
 
@@ -394,7 +395,20 @@ struct zflac_batch {
     std::vector<uint32_t> pipe_who;
     uint32_t* pipe_pin = nullptr;
     zflac_timings timings = {};
+    // zflac_hip_batch_export: the per-row table goes through exp_pin (pinned) into exp_rows
+    // with an async copy on the export's stream. ev_exp_copy marks that copy (the next export
+    // waits for it on the host before it refills exp_pin), ev_exp the kernel (the next export's
+    // stream waits for it before it overwrites exp_rows; while exp_pending, so do the next
+    // run's streams before they overwrite the samples, and the destructor on the host).
+    zflac::ExportRow* exp_pin = nullptr;
+    zflac::DevBuf<zflac::ExportRow> exp_rows;
+    hipEvent_t ev_exp_copy = nullptr, ev_exp = nullptr;
+    hipEvent_t ev_exp_t[2] = {};  // ZFLAC_FLAG_TIMING: around a synchronous export
+    bool exp_any = false;      // ev_exp_copy / ev_exp have been recorded
+    bool exp_pending = false;  // an export on a caller's stream may still read the samples
+    double export_ms = -1;
     ~zflac_batch() {
+        if (exp_pending) (void)hipEventSynchronize(ev_exp);  // a caller's stream may still read the samples
         if (stream) (void)hipStreamSynchronize(stream);  // a submitted run may still use the buffers
         if (ev_done) (void)hipEventSynchronize(ev_done);  // ... on its run stream
         if (md5_pending) {  // still in the md5 hub: flush it, then let the hash finish
@@ -416,6 +430,11 @@ struct zflac_batch {
         if (ev_done) (void)hipEventDestroy(ev_done);
         if (ev_md5) (void)hipEventDestroy(ev_md5);
         if (pipe_pin) (void)hipHostFree(pipe_pin);
+        if (exp_pin) (void)hipHostFree(exp_pin);
+        if (ev_exp_copy) (void)hipEventDestroy(ev_exp_copy);
+        if (ev_exp) (void)hipEventDestroy(ev_exp);
+        for (auto& e : ev_exp_t)
+            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (front) (void)hipStreamDestroy(front);
         if (front_join) (void)hipEventDestroy(front_join);
@@ -1332,6 +1351,11 @@ void submit_batch(zflac_batch* b) {
     // synchronized before they return. A marker recorded there would sit in a hardware queue
     // it may share with a run or md5 hub stream, behind a hash of several milliseconds.)
     b->rs = next_run_stream(b->device);
+    if (b->exp_pending) {  // an export on a caller's stream still reads the samples this run overwrites
+        ck(hipStreamWaitEvent(b->rs, b->ev_exp, 0));
+        if (b->front) ck(hipStreamWaitEvent(b->front, b->ev_exp, 0));
+        b->exp_pending = false;  // from here on the run's own events cover it
+    }
     for (size_t ci = 0; ci < b->classes.size(); ci++) {
         Class& C = *b->classes[ci];
         C.redone = false;
@@ -2012,6 +2036,99 @@ int zflac_hip_batch_timings_ex(zflac_batch* b, zflac_timings* t, size_t size) {
 }
 
 int zflac_hip_abi_version(void) { return ZFLAC_HIP_ABI_VERSION; }
+
+int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst_device, size_t dst_bytes,
+                           uint64_t* valid_frames, void* stream) {
+    if (!b || !d || !dst_device || d->size != sizeof(zflac_export_desc)) return E_INVALID_ARGUMENT;
+    if (d->dtype > ZFLAC_EXPORT_I32 || d->layout > ZFLAC_LAYOUT_INTERLEAVED || !d->channels || !d->frames)
+        return E_INVALID_ARGUMENT;
+    if (!b->ran || b->submitted) return E_INVALID_ARGUMENT;
+    const size_t n = b->streams.size();
+    const uint64_t T = d->frames, C = d->channels;
+    const uint64_t esz = (d->dtype == ZFLAC_EXPORT_F16 || d->dtype == ZFLAC_EXPORT_BF16) ? 2 : 4;
+    const unsigned __int128 need = (unsigned __int128)n * C * T * esz;  // < 2^64 * 2^16 * 2^64 * 4
+    if (need > (unsigned __int128)dst_bytes) return E_INVALID_ARGUMENT;
+    const uint64_t tiles = (T + EXPORT_TILE - 1) / EXPORT_TILE;
+    if ((unsigned __int128)n * tiles > 0x7FFFFFFFull) return E_INVALID_ARGUMENT;  // gridDim.x
+    for (size_t i = 0; valid_frames && i < n; i++) {
+        const StreamState& s = b->streams[i];
+        const uint64_t start = d->starts ? d->starts[i] : 0;
+        const uint64_t nf = (s.err || !s.info.channels) ? 0 : s.info.n_samples / s.info.channels;
+        valid_frames[i] = nf > start ? std::min(nf - start, T) : 0;
+    }
+    if (n == 0) return E_OK;
+    try {
+        DeviceScope scope(b->device);
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->stream;
+        if (!b->exp_pin) {
+            ck(hipHostMalloc(reinterpret_cast<void**>(&b->exp_pin), n * sizeof(ExportRow), hipHostMallocDefault));
+            b->exp_rows.alloc(n);
+            ck(hipEventCreateWithFlags(&b->ev_exp_copy, hipEventDisableTiming));
+            ck(hipEventCreateWithFlags(&b->ev_exp, hipEventDisableTiming));
+        }
+        if (b->exp_any) {
+            ck(hipEventSynchronize(b->ev_exp_copy));     // the last export's copy has read exp_pin
+            ck(hipStreamWaitEvent(st, b->ev_exp, 0));    // and its kernel exp_rows, before this copy lands
+        }
+        for (size_t i = 0; i < n; i++) {
+            const StreamState& s = b->streams[i];
+            ExportRow r;
+            std::memset(&r, 0, sizeof(r));
+            r.start = d->starts ? d->starts[i] : 0;
+            r.kind = s.info.sample_kind;
+            if (!s.err && s.info.channels && s.dev_samples) {
+                r.nch = s.info.channels;
+                r.n_frames = s.info.n_samples / s.info.channels;
+                if (r.start < r.n_frames) r.src = s.dev_samples;
+            }
+            b->exp_pin[i] = r;
+        }
+        const bool timed = !stream && (b->flags & ZFLAC_FLAG_TIMING);
+        if (timed) {
+            for (auto& e : b->ev_exp_t)
+                if (!e) ck(hipEventCreate(&e));
+            ck(hipEventRecord(b->ev_exp_t[0], st));
+        }
+        ck(hipMemcpyAsync(b->exp_rows.p, b->exp_pin, n * sizeof(ExportRow), hipMemcpyHostToDevice, st));
+        ck(hipEventRecord(b->ev_exp_copy, st));
+        ExportArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.rows = b->exp_rows.p;
+        a.dst = dst_device;
+        a.frames = T;
+        a.channels = (uint32_t)C;
+        a.n_rows = (uint32_t)n;
+        a.tiles = (uint32_t)tiles;
+        const uint64_t row_bytes = (d->layout == ZFLAC_LAYOUT_PLANAR ? T : T * C) * esz;
+        a.vec = (reinterpret_cast<uintptr_t>(dst_device) % 16 == 0 && row_bytes % 16 == 0) ? 1u : 0u;
+        const hipError_t le = launch_export(d->dtype, d->layout, a, st);
+        ck(hipEventRecord(b->ev_exp, st));  // (also after a failed launch: the copy above is enqueued)
+        b->exp_any = true;
+        ck(le);
+        if (timed) ck(hipEventRecord(b->ev_exp_t[1], st));
+        if (stream) {
+            b->exp_pending = true;
+        } else {
+            ck(hipStreamSynchronize(st));
+            if (timed) {
+                float ms = 0;
+                ck(hipEventElapsedTime(&ms, b->ev_exp_t[0], b->ev_exp_t[1]));
+                b->export_ms = ms;
+            }
+        }
+    } catch (const DeviceError&) {
+        return E_DEVICE;
+    } catch (const std::bad_alloc&) {
+        return E_OUT_OF_MEMORY;
+    }
+    return E_OK;
+}
+
+int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
+    if (!b || !ms || b->export_ms < 0) return E_INVALID_ARGUMENT;
+    *ms = b->export_ms;
+    return E_OK;
+}
 
 #ifdef ZFLAC_PROBE
 // Timing-probe build only (tools/probe.sh): cycle counters the decode kernels accumulate
