@@ -12,8 +12,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzflac_hip.so")
 SOURCES = [os.path.join(CSRC, f"decode_k{k}_{lay}{mix}.hip") for k in (1, 2, 0) for lay in ("stereo", "mono", "multi")
            for mix in ("", "_mix")]
-SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip", "host.cpp")]
-HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "md5.hpp", "device_common.h", "decode.inc")]
+SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip",
+                                            "stream_plan.cpp", "pipeline.cpp", "seq_planner.cpp", "md5_host.cpp", "abi.cpp")]
+HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "device_common.h", "launch.h", "stream_plan.h",
+                                           "batch.h", "md5.hpp", "decode.inc")]
 DEPS = SOURCES + HEADERS + [os.path.join(ROOT, "include", "zflac_hip.h")]
 ARCH = os.environ.get("ZFLAC_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -60,9 +62,9 @@ def lib_build_id(path: str | None = None) -> str | None:
 
 
 def _obj_deps(src: str):
-    """Headers a translation unit includes (decode.inc only for the decode units). host.cpp
+    """A unit's own source plus all headers (decode.inc only for the decode units). abi.cpp
     embeds the fingerprint of every source, so it depends on all of them."""
-    if src.endswith("host.cpp"):
+    if src.endswith("abi.cpp"):
         return list(DEPS)
     hdrs = [h for h in HEADERS if not h.endswith("decode.inc") or "decode_k" in src]
     return [src] + hdrs + [os.path.join(ROOT, "include", "zflac_hip.h")]
@@ -78,7 +80,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
         return LIB
     if units:
         build()  # the product objects the variant shares
-        units = set(units) | {"host.cpp"}  # host.cpp embeds the variant's fingerprint
+        units = set(units) | {"abi.cpp"}  # abi.cpp embeds the variant's fingerprint
     objs = []
     tag = "_".join(d.replace("=", "-") for d in defines)
     build_dir = os.path.join(HERE, "_build" + ("_" + tag if tag else ""))
@@ -99,7 +101,9 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
         cmd[1:1] = [f"-D{d}" for d in defines]
         if src.endswith(".hip"):
             cmd[1:1] = ["-x", "hip"]
-        if src.endswith("host.cpp"):
+        if src.endswith("stream_plan.cpp"):  # the GPU-free planner: plain C++, no device pass
+            cmd[1:1] = ["-x", "c++"]
+        if src.endswith("abi.cpp"):
             cmd[1:1] = [f'-DZFLAC_BUILD_ID="src={fp}"']
         if verbose:
             print(" ".join(cmd))

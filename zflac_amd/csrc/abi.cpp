@@ -1,0 +1,410 @@
+// abi.cpp -- the extern "C" ABI of include/zflac_hip.h over the host units (batch.h), the
+// batch's destructor, the build id, and the entry points of the diagnostic builds.
+#include <cstring>
+#include <new>
+
+#include "batch.h"
+#include "launch.h"
+
+using namespace zflac;
+
+zflac_batch::~zflac_batch() {
+    if (exp_pending) (void)hipEventSynchronize(ev_exp);  // a caller's stream may still read the samples
+    if (stream) (void)hipStreamSynchronize(stream);  // a submitted run may still use the buffers
+    if (ev_done) (void)hipEventSynchronize(ev_done);  // ... on its run stream
+    if (md5_pending) {  // still in the md5 hub: flush it, then let the hash finish
+        try {
+            hub_release(this);
+        } catch (...) {
+        }
+        try {
+            hub_forget(this);  // never leave a pointer to this batch in the hub
+        } catch (...) {
+        }
+    }
+    if (md5_hub && ev_md5) (void)hipEventSynchronize(ev_md5);
+    if (front) (void)hipStreamSynchronize(front);
+    classes.clear();
+    for (auto& s : streams) s.override_out.reset();
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ev_done) (void)hipEventDestroy(ev_done);
+    if (ev_md5) (void)hipEventDestroy(ev_md5);
+    if (pipe_pin) (void)hipHostFree(pipe_pin);
+    if (exp_pin) (void)hipHostFree(exp_pin);
+    if (ev_exp_copy) (void)hipEventDestroy(ev_exp_copy);
+    if (ev_exp) (void)hipEventDestroy(ev_exp);
+    for (auto& e : ev_exp_t)
+        if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (front) (void)hipStreamDestroy(front);
+    if (front_join) (void)hipEventDestroy(front_join);
+}
+
+extern "C" {
+
+const char* zflac_hip_error_name(int code) {
+    switch (code) {
+        case 0: return "OK";
+        case 1: return "InvalidSignature";
+        case 2: return "InvalidMetadataHeader";
+        case 3: return "MissingStreaminfo";
+        case 4: return "Unimplemented";
+        case 5: return "InvalidChecksum";
+        case 6: return "InvalidFrameHeader";
+        case 7: return "InconsistentParameters";
+        case 8: return "InvalidCodedNumber";
+        case 9: return "InvalidSubframeHeader";
+        case 10: return "InvalidResidualCodingMethod";
+        case 11: return "EndOfStream";
+        case 12: return "OutOfMemory";
+        case 13: return "DeviceError";
+        case 14: return "InvalidArgument";
+        case 15: return "OutOfDomain";
+        case 16: return "FrameCrcMismatch";
+        default: return "Unknown";
+    }
+}
+
+int zflac_hip_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+const char* zflac_hip_version(void) { return "zflac_hip gfx950 r4"; }
+
+#ifndef ZFLAC_BUILD_ID
+#define ZFLAC_BUILD_ID "unknown"
+#endif
+const char* zflac_hip_build_id(void) { return ZFLAC_BUILD_ID; }
+
+int zflac_hip_batch_create(const zflac_stream* streams, size_t n, int device, int flags, zflac_batch** out) {
+    return create_batch(streams, n, device, flags, out);
+}
+
+// After a failed submit: the work already enqueued (on the batch stream and, with
+// ZFLAC_FRONT_PRIORITY, the front stream) may still use the candidate buffers a retry
+// reallocates.
+static void drain_failed_submit(zflac_batch* b) {
+    try {
+        hub_forget(b);
+    } catch (...) {
+    }
+    (void)hipStreamSynchronize(b->stream);
+    if (b->rs) (void)hipStreamSynchronize(b->rs);
+    if (b->front) (void)hipStreamSynchronize(b->front);
+    b->rs = b->stream;
+    b->submitted = false;
+}
+
+int zflac_hip_batch_submit(zflac_batch* b) {
+    if (!b || b->submitted) return E_INVALID_ARGUMENT;
+    b->ran = false;
+    try {
+        b->submit_t0 = now_ms();
+        b->submitted = true;
+        submit_batch(b);
+    } catch (const DeviceError&) {
+        drain_failed_submit(b);
+        return E_DEVICE;
+    } catch (const std::bad_alloc&) {
+        drain_failed_submit(b);
+        return E_OUT_OF_MEMORY;
+    } catch (const std::exception&) {
+        drain_failed_submit(b);
+        return E_DEVICE;
+    }
+    return E_OK;
+}
+
+int zflac_hip_batch_wait(zflac_batch* b) {
+    if (!b || !b->submitted) return E_INVALID_ARGUMENT;
+    b->submitted = false;
+    int rc = E_OK;
+    try {
+        finish_batch(b);
+        b->timings.run_wall_ms = now_ms() - b->submit_t0;
+        b->ran = true;
+    } catch (const DeviceError&) {
+        rc = E_DEVICE;
+    } catch (const std::bad_alloc&) {
+        rc = E_OUT_OF_MEMORY;
+    } catch (const std::exception&) {
+        rc = E_DEVICE;
+    }
+    if (rc != E_OK && b->md5_pending) {  // failed before the hub released this run
+        try {
+            hub_forget(b);
+        } catch (...) {
+        }
+    }
+    return rc;
+}
+
+int zflac_hip_batch_ready(zflac_batch* b) {
+    if (!b || !b->submitted) return -E_INVALID_ARGUMENT;
+    hipError_t e = hipEventQuery(b->ev_done);
+    if (e == hipSuccess && b->md5_hub) {
+        try {
+            Md5Hub& h = md5_hub(b->device);
+            std::lock_guard<std::mutex> lock(h.mu);
+            if (b->md5_pending) {  // decoded, hash not launched: launch it if the hub is idle
+                if (!h.any || hipEventQuery(h.last) == hipSuccess) hub_flush(h);
+                return 0;
+            }
+            // the hub launch holding this run failed (possibly another thread's flush): ev_md5
+            // was never recorded for this run, so it must not be queried
+            if (b->md5_failed) return -E_DEVICE;
+        } catch (const DeviceError&) {
+            return -E_DEVICE;
+        }
+        e = hipEventQuery(b->ev_md5);
+    }
+    if (e == hipSuccess) return 1;
+    if (e == hipErrorNotReady) return 0;
+    return -E_DEVICE;
+}
+
+int zflac_hip_batch_run(zflac_batch* b) {
+    const int rc = zflac_hip_batch_submit(b);
+    return rc ? rc : zflac_hip_batch_wait(b);
+}
+
+size_t zflac_hip_batch_size(zflac_batch* b) { return b ? b->streams.size() : 0; }
+
+int zflac_hip_batch_info(zflac_batch* b, size_t i, zflac_info* info) {
+    if (!b || !b->ran || i >= b->streams.size()) return E_INVALID_ARGUMENT;
+    const StreamState& s = b->streams[i];
+    if (info) *info = s.info;
+    return s.err;
+}
+
+const void* zflac_hip_batch_device_samples(zflac_batch* b, size_t i) {
+    if (!b || !b->ran || i >= b->streams.size() || b->streams[i].err) return nullptr;
+    return b->streams[i].dev_samples;
+}
+
+int zflac_hip_batch_read(zflac_batch* b, size_t i, void* out, size_t out_bytes, int verify_md5) {
+    if (!b || !b->ran || i >= b->streams.size()) return E_INVALID_ARGUMENT;
+    StreamState& s = b->streams[i];
+    if (s.err) return s.err;
+    if (out_bytes < s.info.samples_bytes || (!out && s.info.samples_bytes)) return E_INVALID_ARGUMENT;
+    try {
+        ck(hipSetDevice(b->device));
+        // a device verdict stands in for the host hash (a mismatch is already s.err)
+        return read_samples(b, s, out, verify_md5 && !s.md5_dev);  // InvalidChecksum at :279-280
+    } catch (const DeviceError&) {
+        return E_DEVICE;
+    } catch (const std::exception&) {  // std::system_error: the hashing thread could not start
+        return E_DEVICE;
+    }
+}
+
+int zflac_hip_batch_md5(zflac_batch* b, size_t i, uint8_t* digest) {
+    if (!b || !b->ran || i >= b->streams.size() || !digest) return E_INVALID_ARGUMENT;
+    const StreamState& s = b->streams[i];
+    if (!s.md5_dev) return E_INVALID_ARGUMENT;
+    std::memcpy(digest, s.md5_dig, 16);
+    return E_OK;
+}
+
+int zflac_hip_batch_timings(zflac_batch* b, zflac_timings* t) {
+    return zflac_hip_batch_timings_ex(b, t, ZFLAC_TIMINGS_V1_SIZE);
+}
+
+int zflac_hip_batch_timings_ex(zflac_batch* b, zflac_timings* t, size_t size) {
+    if (!b || !t || size == 0) return E_INVALID_ARGUMENT;
+    // the caller's struct may be older (shorter) or newer (longer) than this library's
+    std::memcpy(t, &b->timings, std::min(size, sizeof(zflac_timings)));
+    if (size > sizeof(zflac_timings)) std::memset(reinterpret_cast<uint8_t*>(t) + sizeof(zflac_timings), 0,
+                                                  size - sizeof(zflac_timings));
+    return b->have_timing ? E_OK : E_INVALID_ARGUMENT;  // the host wall-clock fields are always filled
+}
+
+int zflac_hip_abi_version(void) { return ZFLAC_HIP_ABI_VERSION; }
+
+int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst_device, size_t dst_bytes,
+                           uint64_t* valid_frames, void* stream) {
+    if (!b || !d || !dst_device || d->size != sizeof(zflac_export_desc)) return E_INVALID_ARGUMENT;
+    if (d->dtype > ZFLAC_EXPORT_I32 || d->layout > ZFLAC_LAYOUT_INTERLEAVED || !d->channels || !d->frames)
+        return E_INVALID_ARGUMENT;
+    if (!b->ran || b->submitted) return E_INVALID_ARGUMENT;
+    const size_t n = b->streams.size();
+    const uint64_t T = d->frames, C = d->channels;
+    const uint64_t esz = (d->dtype == ZFLAC_EXPORT_F16 || d->dtype == ZFLAC_EXPORT_BF16) ? 2 : 4;
+    const unsigned __int128 need = (unsigned __int128)n * C * T * esz;  // < 2^64 * 2^16 * 2^64 * 4
+    if (need > (unsigned __int128)dst_bytes) return E_INVALID_ARGUMENT;
+    const uint64_t tiles = (T + EXPORT_TILE - 1) / EXPORT_TILE;
+    if ((unsigned __int128)n * tiles > 0x7FFFFFFFull) return E_INVALID_ARGUMENT;  // gridDim.x
+    for (size_t i = 0; valid_frames && i < n; i++) {
+        const StreamState& s = b->streams[i];
+        const uint64_t start = d->starts ? d->starts[i] : 0;
+        const uint64_t nf = (s.err || !s.info.channels) ? 0 : s.info.n_samples / s.info.channels;
+        valid_frames[i] = nf > start ? std::min(nf - start, T) : 0;
+    }
+    if (n == 0) return E_OK;
+    try {
+        DeviceScope scope(b->device);
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->stream;
+        if (!b->exp_pin) {
+            ck(hipHostMalloc(reinterpret_cast<void**>(&b->exp_pin), n * sizeof(ExportRow), hipHostMallocDefault));
+            b->exp_rows.alloc(n);
+            ck(hipEventCreateWithFlags(&b->ev_exp_copy, hipEventDisableTiming));
+            ck(hipEventCreateWithFlags(&b->ev_exp, hipEventDisableTiming));
+        }
+        if (b->exp_any) {
+            ck(hipEventSynchronize(b->ev_exp_copy));     // the last export's copy has read exp_pin
+            ck(hipStreamWaitEvent(st, b->ev_exp, 0));    // and its kernel exp_rows, before this copy lands
+        }
+        for (size_t i = 0; i < n; i++) {
+            const StreamState& s = b->streams[i];
+            ExportRow r;
+            std::memset(&r, 0, sizeof(r));
+            r.start = d->starts ? d->starts[i] : 0;
+            r.kind = s.info.sample_kind;
+            if (!s.err && s.info.channels && s.dev_samples) {
+                r.nch = s.info.channels;
+                r.n_frames = s.info.n_samples / s.info.channels;
+                if (r.start < r.n_frames) r.src = s.dev_samples;
+            }
+            b->exp_pin[i] = r;
+        }
+        const bool timed = !stream && (b->flags & ZFLAC_FLAG_TIMING);
+        if (timed) {
+            for (auto& e : b->ev_exp_t)
+                if (!e) ck(hipEventCreate(&e));
+            ck(hipEventRecord(b->ev_exp_t[0], st));
+        }
+        ck(hipMemcpyAsync(b->exp_rows.p, b->exp_pin, n * sizeof(ExportRow), hipMemcpyHostToDevice, st));
+        ck(hipEventRecord(b->ev_exp_copy, st));
+        ExportArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.rows = b->exp_rows.p;
+        a.dst = dst_device;
+        a.frames = T;
+        a.channels = (uint32_t)C;
+        a.n_rows = (uint32_t)n;
+        a.tiles = (uint32_t)tiles;
+        const uint64_t row_bytes = (d->layout == ZFLAC_LAYOUT_PLANAR ? T : T * C) * esz;
+        a.vec = (reinterpret_cast<uintptr_t>(dst_device) % 16 == 0 && row_bytes % 16 == 0) ? 1u : 0u;
+        const hipError_t le = launch_export(d->dtype, d->layout, a, st);
+        ck(hipEventRecord(b->ev_exp, st));  // (also after a failed launch: the copy above is enqueued)
+        b->exp_any = true;
+        ck(le);
+        if (timed) ck(hipEventRecord(b->ev_exp_t[1], st));
+        if (stream) {
+            b->exp_pending = true;
+        } else {
+            ck(hipStreamSynchronize(st));
+            if (timed) {
+                float ms = 0;
+                ck(hipEventElapsedTime(&ms, b->ev_exp_t[0], b->ev_exp_t[1]));
+                b->export_ms = ms;
+            }
+        }
+    } catch (const DeviceError&) {
+        return E_DEVICE;
+    } catch (const std::bad_alloc&) {
+        return E_OUT_OF_MEMORY;
+    }
+    return E_OK;
+}
+
+int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
+    if (!b || !ms || b->export_ms < 0) return E_INVALID_ARGUMENT;
+    *ms = b->export_ms;
+    return E_OK;
+}
+
+#ifdef ZFLAC_PROBE
+// Timing-probe build only (tools/probe.sh): cycle counters the decode kernels accumulate
+// behind the dummy store region of the first class; zeroed after reading.
+extern "C" int zflac_hip_probe(zflac_batch* b, unsigned long long* out, int n) {
+    if (!b || b->classes.empty() || n > (int)(PROBE_BYTES / 8)) return E_INVALID_ARGUMENT;
+    auto& C = *b->classes[0];
+    uint8_t* p = reinterpret_cast<uint8_t*>(C.dummy.p) + DUMMY_BYTES;
+    if (hipMemcpy(out, p, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return E_DEVICE;
+    if (hipMemset(p, 0, PROBE_BYTES) != hipSuccess) return E_DEVICE;
+    return E_OK;
+}
+#endif
+
+#ifdef ZFLAC_REPLAY
+// Diagnostic build only (tools/replay.py): re-enqueue parts of each batch's last run `reps`
+// times, batch i on its own run stream, with no host work in between, and return the wall
+// time: what = 1 walk, 2 decode, 3 walk + decode, 4 the whole run (enqueue_class: fills, scan,
+// compact, walk, decode, verify, read-backs). Separates the device's throughput for each part
+// from the host side of submit / wait. Outputs are rewritten with the same values.
+extern "C" int zflac_hip_replay(zflac_batch** bs, int nb, int reps, int what, double* ms) {
+    try {
+        if (nb <= 0 || !bs || !ms) return E_INVALID_ARGUMENT;
+        ck(hipSetDevice(bs[0]->device));
+        for (int i = 0; i < nb; i++) {  // one run stream (hardware queue) per batch, as submit
+            ck(hipStreamSynchronize(bs[i]->rs));
+            bs[i]->rs = next_run_stream(bs[i]->device);
+        }
+        const double t0 = now_ms();
+        for (int r = 0; r < reps; r++) {
+            for (int i = 0; i < nb; i++) {
+                zflac_batch* b = bs[i];
+                Class& C = *b->classes[0];
+                if (what == 4) {
+                    enqueue_class(b, C, false, false);
+                    continue;
+                }
+                if (what >= 8) {  // the front alone: 8 k_scan, 16 k_scan + k_scan_chunks + k_compact
+                    const ScanArgs sa = scan_args(C);
+                    ck(launch_scan(sa, b->rs));
+                    if (what == 16) {
+                        ck(launch_scan_chunks(C.chunk_cnt.p, C.chunk_units.p, sa.n_chunks, C.chunk_off.p,
+                                              C.chunk_uoff.p, C.misc.p, b->rs));
+                        ck(launch_compact(compact_args(C), b->rs));
+                    }
+                    continue;
+                }
+                DecodeArgs da = decode_args(C);
+                da.full_mask = C.full_mask;
+                const uint32_t mf = std::min(C.grid_frames, C.cap);
+                if (what & 1) ck(launch_walk_k1(da, mf, b->rs));
+                if (what & 2) ck(launch_decode_k1_stereo(da, mf, b->rs));
+            }
+        }
+        for (int i = 0; i < nb; i++) ck(hipStreamSynchronize(bs[i]->rs));
+        *ms = now_ms() - t0;
+        for (int i = 0; i < nb; i++) bs[i]->rs = bs[i]->stream;
+        return E_OK;
+    } catch (const DeviceError&) {
+        return E_DEVICE;
+    }
+}
+#endif
+
+void zflac_hip_batch_destroy(zflac_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    delete b;
+}
+
+int zflac_hip_open(const uint8_t* buf, size_t len, int device, zflac_batch** out_batch, zflac_info* info) {
+    return zflac_hip_open_ex(buf, len, device, 0, out_batch, info);
+}
+
+int zflac_hip_open_ex(const uint8_t* buf, size_t len, int device, int flags, zflac_batch** out_batch,
+                      zflac_info* info) {
+    if (!out_batch) return E_INVALID_ARGUMENT;
+    zflac_stream s{buf, len};
+    int rc = create_batch(&s, 1, device, flags, out_batch);
+    if (rc) return rc;
+    rc = zflac_hip_batch_run(*out_batch);
+    if (rc) return rc;
+    return zflac_hip_batch_info(*out_batch, 0, info);
+}
+
+int zflac_hip_read(zflac_batch* b, void* out_samples, size_t out_bytes) {
+    return zflac_hip_batch_read(b, 0, out_samples, out_bytes, 1);
+}
+
+void zflac_hip_close(zflac_batch* b) { zflac_hip_batch_destroy(b); }
+
+}  // extern "C"

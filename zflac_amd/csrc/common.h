@@ -1,7 +1,15 @@
-// common.h -- descriptors shared by the host planner (host.cpp) and the HIP kernels
-// (kernels.hip). Plain structs, identical layout on both sides.
+// common.h -- descriptors shared by the host units (stream_plan.cpp, pipeline.cpp,
+// seq_planner.cpp, md5_host.cpp, abi.cpp) and the HIP kernels (the .hip units). Plain
+// structs, identical layout on both sides; no HIP header, so plain C++ can include it.
 #pragma once
 #include <cstdint>
+
+// Functions the host and the kernels share: both under hipcc, plain C++ elsewhere.
+#ifdef __HIPCC__
+#define ZFLAC_HD __host__ __device__
+#else
+#define ZFLAC_HD
+#endif
 
 namespace zflac {
 
@@ -156,7 +164,7 @@ constexpr uint32_t SPARSE_DECODE_BLOCKS = 256;
 // Bit of a k_decode launch (history bucket MB, MIX kernels) in DecodeArgs::bucket_used /
 // full_mask: 8 -> 1, 4 -> 2, 16 -> 4, 32 -> 8, MIX 8 -> 16, MIX 32 -> 32, 12 -> 64. The order-8 launch
 // always runs (it classifies every wave).
-__host__ __device__ inline constexpr uint32_t bucket_bit(uint32_t mb, bool mix) {
+ZFLAC_HD inline constexpr uint32_t bucket_bit(uint32_t mb, bool mix) {
     return mix ? (mb <= 8 ? 16u : 32u)
                : (mb == 8 ? 1u : (mb == 4 ? 2u : (mb == 16 ? 4u : (mb == 12 ? 64u : 8u))));
 }
@@ -182,7 +190,7 @@ struct Md5Job {
                              // this run (the sequential planner decodes it later), no hash
 };
 
-// Jobs of several runs for one k_md5_multi launch (the md5 hub, host.cpp): segment s is
+// Jobs of several runs for one k_md5_multi launch (the md5 hub, md5_host.cpp): segment s is
 // jobs[s][0 .. start[s+1] - start[s]), its digests go to dig[s].
 constexpr int MD5_MAX_SEGS = 16;
 struct Md5Segs {

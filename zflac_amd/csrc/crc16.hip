@@ -10,6 +10,7 @@
 // slice-by-4 tables in LDS), multiplies its remainder by x^(8 * bytes after its piece) and
 // the wave xor-reduces. HBM-bound: each frame byte is read once.
 #include "device_common.h"
+#include "launch.h"
 
 namespace zflac {
 namespace {

@@ -23,6 +23,7 @@
 // more to land and the per-sample work is ALU + LDS reads. A lane that would run its ring
 // dry redoes the chunk on the generic path (synchronous refills).
 #include "device_common.h"
+#include "launch.h"
 
 namespace zflac {
 

@@ -33,6 +33,7 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "launch.h"
 
 namespace zflac {
 namespace {

@@ -1,0 +1,47 @@
+// launch.h -- every launch_* entry of the .hip units, declared once: the unit that defines
+// one and the host units that call it include this header, so a signature that drifts
+// between the two is a compile error.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "common.h"
+
+namespace zflac {
+
+// scan.hip
+hipError_t launch_scan(const ScanArgs& a, hipStream_t st);
+hipError_t launch_scan_chunks(const uint32_t* cnt, const unsigned long long* units, uint32_t n, uint32_t* off,
+                              unsigned long long* uoff, uint32_t* n_frames, hipStream_t st);
+hipError_t launch_compact(const CompactArgs& a, hipStream_t st);
+hipError_t launch_sync_list(const SyncListArgs& a, hipStream_t st);
+hipError_t launch_verify(const VerifyArgs& a, uint32_t max_items, hipStream_t st);
+
+// decode_k{0,1,2}_{stereo,mono,multi}.hip: the bucket launches of one (container kind, layout);
+// each ends with its _mix unit's (constant / verbatim subframes). launch_walk_k*: k_walk of the
+// container (defined in the stereo unit).
+using DecodeLaunch = hipError_t(const DecodeArgs& a, uint32_t max_frames, hipStream_t st);
+DecodeLaunch launch_decode_k0_stereo, launch_decode_k0_mono, launch_decode_k0_multi;
+DecodeLaunch launch_decode_k1_stereo, launch_decode_k1_mono, launch_decode_k1_multi;
+DecodeLaunch launch_decode_k2_stereo, launch_decode_k2_mono, launch_decode_k2_multi;
+DecodeLaunch launch_decode_k0_stereo_mix, launch_decode_k0_mono_mix, launch_decode_k0_multi_mix;
+DecodeLaunch launch_decode_k1_stereo_mix, launch_decode_k1_mono_mix, launch_decode_k1_multi_mix;
+DecodeLaunch launch_decode_k2_stereo_mix, launch_decode_k2_mono_mix, launch_decode_k2_multi_mix;
+DecodeLaunch launch_walk_k0, launch_walk_k1, launch_walk_k2;
+
+// walk_wave.hip
+hipError_t launch_walk_wave(int kind, const DecodeArgs& a, uint32_t max_frames, hipStream_t st);
+
+// crc16.hip
+hipError_t launch_crc16(const Crc16Args& a, uint32_t max_frames, hipStream_t st);
+
+// md5.hip. coop_mode: the Md5Mode every job shares with 16-byte aligned samples (the
+// cooperative-load kernel), or -1 (lane-per-stream loads)
+hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode);
+hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode);
+
+// export.hip
+hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st);
+
+}  // namespace zflac

@@ -8,13 +8,13 @@
 //
 // MD5 (RFC 1321) is a chain over 64-byte blocks, so one stream is one lane: a batch of
 // many streams fills waves, one long stream does not (the host keeps the CPU hash for
-// that case, see host.cpp). Per block: 16 message words from HBM (loaded one unit ahead
+// that case, see md5_host.cpp). Per block: 16 message words from HBM (loaded one unit ahead
 // of the compression that uses them), 64 dependent rounds of ~5 VALU ops (gfx950's
 // v_bitop3_b32 makes each round function one instruction).
 //
 // A lane's time is its stream's chain (~4 dependent VALU ops per round), so a batch's hash
 // takes about as long as its longest stream, whatever the stream count. Runs are hashed by
-// the device's md5 hub (host.cpp): one launch over the certified streams of several runs,
+// the device's md5 hub (md5_host.cpp): one launch over the certified streams of several runs,
 // on a stream of its own, while the runs of other batches decode. That launch is k_md5_coop
 // (a wave reads its 64 streams' data cooperatively through LDS, hash_units_coop) when every
 // job shares one mode and 16-byte alignment, else k_md5_multi (each lane its own loads).
@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launch.h"
 
 namespace zflac {
 namespace {
@@ -341,7 +342,7 @@ __device__ __forceinline__ void md5_job(const Md5Job& j, uint32_t* __restrict__ 
 }
 
 // The jobs of several runs (one segment each: several batches' runs hashed by one launch,
-// md5 hub in host.cpp): lane t's job is job t - start[s] of the segment s holding t.
+// md5 hub in md5_host.cpp): lane t's job is job t - start[s] of the segment s holding t.
 __device__ __forceinline__ const Md5Job* seg_job(const Md5Segs& sg, uint32_t t, uint32_t*& out) {
     if (t >= sg.start[sg.nseg]) return nullptr;
     uint32_t s = 0;

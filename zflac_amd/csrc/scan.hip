@@ -9,6 +9,7 @@
 //                   (src/zflac.zig:340-581) would walk? Streams failing it are finished by
 //                   the host's sequential planner.
 #include "device_common.h"
+#include "launch.h"
 
 #ifndef ZFLAC_SCAN_AUX
 #define ZFLAC_SCAN_AUX 0  // cache policy bits of k_scan's loads (experiment: 2 = nontemporal)

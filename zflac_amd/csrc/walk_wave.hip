@@ -22,6 +22,7 @@
 // with the true one within the segment ~70 % of the time, so ~4 rounds settle the wave, and
 // one pass covers 4096 bits, a whole partition of C3.
 #include "device_common.h"
+#include "launch.h"
 
 namespace zflac {
 namespace {
