@@ -215,6 +215,55 @@ int zflac_hip_batch_export(zflac_batch *b, const zflac_export_desc *d, void *dst
  * ZFLAC_FLAG_TIMING (table copy + k_export); ZFLAC_E_INVALID_ARGUMENT when there is none. */
 int zflac_hip_batch_export_ms(zflac_batch *b, double *ms);
 
+/* ---- dense device export at one sample rate -------------------------------------- */
+/* zflac_hip_batch_export with every row resampled to `sample_rate` by one HIP kernel
+ * (k_resample), so a batch of mixed-rate streams becomes one tensor with one time base.
+ * A stream of rate fin (zflac_info.sample_rate) goes to fout = sample_rate through a polyphase
+ * Kaiser-windowed sinc: g = gcd(fin, fout), M = fin / g, L = fout / g,
+ * s = min(1, L / M) * rolloff, W = ceil(zeros / s), K = 2 W + 1. Output frame m is
+ *   y[m] = sum_{k < K} h[r][k] * x[q - W + k],  q = floor(m M / L), r = (m M) mod L,
+ * x the sample as ZFLAC_EXPORT_F32 has it, zero outside the stream, and
+ *   h[r][k] = u[r][k] / sum_k u[r][k],  u[r][k] = s sinc(t) kaiser(t),  t = s ((k - W) - r / L),
+ *   kaiser(t) = I0(beta sqrt(1 - (t / zeros)^2)) / I0(beta) for |t| < zeros, 0 otherwise
+ * (tables in double, rounded once to float; sums in f32 with fused multiply-adds in ascending
+ * k, so a frame's value does not depend on the window it is exported in; no renormalisation at
+ * the stream's edges). The resampled stream has ceil(frames * L / M) frames. A stream already at
+ * `sample_rate` is not filtered: its row is bit-identical to zflac_hip_batch_export's. A stream
+ * whose rate is 0 exports a zero row of valid length 0. */
+typedef struct zflac_resample_desc {
+    uint32_t size;          /* sizeof(zflac_resample_desc) */
+    uint8_t dtype, layout;  /* ZFLAC_EXPORT_F32 / _F16 / _BF16 (rounded from the f32 sum as the plain
+                               export rounds), ZFLAC_LAYOUT_* */
+    uint16_t channels;      /* C >= 1 */
+    uint64_t frames;        /* T >= 1, frames of the resampled streams */
+    const uint64_t *starts; /* host array, one per stream, in frames of the resampled stream, or NULL */
+    uint32_t sample_rate;   /* the target rate, 1 .. 1048575 */
+    uint16_t zeros;         /* zero crossings of the sinc on each side, >= 1 (16 is a good default) */
+    uint16_t reserved;      /* must be 0 */
+    double rolloff;         /* 0 < rolloff <= 1: the cutoff as a fraction of the lower Nyquist rate (0.85) */
+    double beta;            /* Kaiser window shape, >= 0 (8.555504641634386) */
+} zflac_resample_desc;
+/* The contract of zflac_hip_batch_export (destination, stream semantics, channel fitting, zero
+ * fill, error rows, every element written), with frames, starts and valid_frames counted in
+ * frames of the resampled streams: valid_frames[i] = clamp(ceil(n_i L_i / M_i) - starts[i], 0, T).
+ * ZFLAC_E_INVALID_ARGUMENT (nothing written): whatever the plain export rejects,
+ * ZFLAC_EXPORT_I32, a sample_rate of 0 or above 1048575, zeros of 0, rolloff or beta out of
+ * range, reserved != 0, and two limits of the call: a stream whose K exceeds 4096 taps, and
+ * tables (L * K floats per distinct source rate among the streams that are filtered) that
+ * together exceed 4 Mi floats. A caller with such streams exports them apart or with a
+ * narrower filter. The batch keeps each table it builds in device memory (one per distinct
+ * source rate, target rate, zeros, rolloff, beta) until it is destroyed, or until a later
+ * call's tables would take it past 4 Mi floats; an export with parameters it has met builds
+ * nothing. zflac_hip_batch_export_ms reports the last synchronous export of either kind. */
+int zflac_hip_batch_export_resampled(zflac_batch *b, const zflac_resample_desc *d, void *dst_device,
+                                     size_t dst_bytes, uint64_t *valid_frames, void *stream);
+/* Frames of a stream of n_frames at rate_in once resampled to rate_out: ceil(n_frames * L / M);
+ * 0 when either rate is 0. Host arithmetic, no GPU needed. */
+uint64_t zflac_hip_resampled_frames(uint64_t n_frames, uint32_t rate_in, uint32_t rate_out);
+/* The batch's resampling tables: how many it has built since it was created and how many
+ * floats it holds now (either pointer may be NULL). */
+int zflac_hip_batch_resample_tables(zflac_batch *b, uint64_t *built, uint64_t *held_floats);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -253,7 +302,9 @@ const char *zflac_hip_build_id(void);
  * 5: zflac_timings.sequential_streams (was reserved0); total-unknown streams certified by the
  *    parallel pass.
  *    Added without a bump (no existing struct or signature changed): zflac_export_desc,
- *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*. */
+ *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*;
+ *    zflac_resample_desc, zflac_hip_batch_export_resampled, zflac_hip_resampled_frames,
+ *    zflac_hip_batch_resample_tables. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -15,7 +15,14 @@ region). Reported per variant: min / median / max milliseconds and the fraction 
 HBM peak that (bytes read + bytes written, from the shapes) / time amounts to. Those intervals
 hold the host side of a call from Python as well (the device idles while the call is prepared), so
 each variant is also timed by the library's own HIP events around the table copy and the kernel
-("device", synchronous exports through the C call)."""
+("device", synchronous exports through the C call).
+
+    python tools/bench_export.py --resampled [--rate 16000] [--out profiles/resample_bench.json]
+
+times the resampled export (k_resample) instead: the same shard (44.1 kHz) to --rate, planar f32
+and planar f16, alternating in every iteration with the plain planar-f32 export (k_export) as
+the yardstick, by the same two clocks. It also writes down what the kernel as built reads
+from LDS for that many output frames, for comparison with the time."""
 from __future__ import annotations
 
 import argparse
@@ -41,8 +48,12 @@ def main():
     ap.add_argument("--streams", type=int, default=bench.STREAMS_PER_GPU)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "export_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--resampled", action="store_true", help="time k_resample beside k_export planar f32")
+    ap.add_argument("--rate", type=int, default=16000, help="--resampled: the target rate")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "resample_bench.json" if a.resampled else "export_bench.json")
     assert a.iters >= 50, "at least 50 timed exports per variant"
 
     streams = bench.make_shard(0, 1, a.streams)
@@ -55,6 +66,8 @@ def main():
     C = 2
     T = bench.FRAMES_PER_STREAM * 4096
     side = torch.cuda.Stream()
+    if a.resampled:
+        return resampled(a, batch, tm, side)
 
     variants = {
         "planar_f32": dict(dtype=torch.float32, layout="planar"),
@@ -146,6 +159,95 @@ def main():
         f.write("\n")
     print(json.dumps(res))
     return 0 if res["planar_f32_not_slower_than_torch"] else 1
+
+
+LDS_PEAK = 78e12  # bytes/s, aggregate (256 CUs x 128 B/clk x 2.4 GHz)
+
+
+def resampled(a, batch, tm, side):
+    """k_resample (planar f32, planar f16) alternating with k_export planar f32."""
+    import ctypes
+    import math
+
+    from zflac_amd import _lib
+
+    B, C = len(batch), 2
+    T_in = bench.FRAMES_PER_STREAM * 4096
+    fin = batch.info(0)[1].sample_rate
+    g = math.gcd(fin, a.rate)
+    L, M = a.rate // g, fin // g
+    s = min(1.0, L / M) * 0.85
+    K = 2 * math.ceil(16 / s) + 1
+    T = batch._L.zflac_hip_resampled_frames(T_in, fin, a.rate)
+    variants = {
+        "k_export_planar_f32": dict(dtype=torch.float32, frames=T_in),
+        "k_resample_planar_f32": dict(dtype=torch.float32, frames=T, sample_rate=a.rate),
+        "k_resample_planar_f16": dict(dtype=torch.float16, frames=T, sample_rate=a.rate),
+    }
+    outs, nbytes = {}, {}
+    with torch.cuda.stream(side):
+        for name, kw in variants.items():
+            outs[name] = torch.empty((B, C, kw["frames"]), dtype=kw["dtype"], device="cuda")
+            nbytes[name] = B * T_in * C * 2 + outs[name].numel() * outs[name].element_size()
+    side.synchronize()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        fn()
+        e1.record(side)
+        side.synchronize()
+        return e0.elapsed_time(e1)
+
+    times = {k: [] for k in variants}
+    with torch.cuda.stream(side):
+        for it in range(a.warmup + a.iters):
+            for name, kw in variants.items():
+                ms = timed(lambda: tensor.export(batch, channels=C, out=outs[name], stream=side, **kw))
+                if it >= a.warmup:
+                    times[name].append(ms)
+    # the device side alone: synchronous exports through the C calls, the library's own HIP events
+    device_ms = {k: [] for k in variants}
+    ms = ctypes.c_double()
+    for it in range(a.warmup + a.iters):
+        for name, kw in variants.items():
+            o = outs[name]
+            code = _lib.EXPORT_F32 if kw["dtype"] == torch.float32 else _lib.EXPORT_F16
+            if "sample_rate" in kw:
+                d = _lib.zflac_resample_desc(ctypes.sizeof(_lib.zflac_resample_desc), code, _lib.LAYOUT_PLANAR, C,
+                                             kw["frames"], None, a.rate, 16, 0, 0.85, 8.555504641634386)
+                rc = batch._L.zflac_hip_batch_export_resampled(batch._h, ctypes.byref(d), o.data_ptr(),
+                                                               o.numel() * o.element_size(), None, None)
+            else:
+                d = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), code, _lib.LAYOUT_PLANAR, C,
+                                           kw["frames"], None)
+                rc = batch._L.zflac_hip_batch_export(batch._h, ctypes.byref(d), o.data_ptr(),
+                                                     o.numel() * o.element_size(), None, None)
+            assert rc == 0 and batch._L.zflac_hip_batch_export_ms(batch._h, ctypes.byref(ms)) == 0
+            if it >= a.warmup:
+                device_ms[name].append(ms.value)
+    # what the kernel as built reads from LDS: per output frame and tap one tap and C samples
+    lds_read = B * T * K * (1 + C) * 4
+    res = {"build_id": zflac_amd.build_id(), "device": torch.cuda.get_device_name(0), "streams": B, "channels": C,
+           "frames_in": T_in, "rate_in": fin, "rate_out": a.rate, "frames_out": T, "L": L, "M": M, "K": K,
+           "iters": a.iters, "warmup": a.warmup, "hbm_peak_bytes_per_s": HBM_PEAK, "lds_peak_bytes_per_s": LDS_PEAK,
+           "macs": B * T * C * K, "lds_read_bytes_as_built": lds_read, "lds_read_ms_at_peak": lds_read / LDS_PEAK * 1e3,
+           "decode_step_ms": {"total": tm.total_ms, "scan": tm.scan_ms, "walk": tm.walk_ms, "decode": tm.decode_ms,
+                              "verify": tm.verify_ms} if tm is not None else None,
+           "variants": {}}
+    for name in variants:
+        ts, ds = times[name], device_ms[name]
+        res["variants"][name] = {
+            "min_ms": min(ts), "median_ms": statistics.median(ts), "max_ms": max(ts), "hbm_bytes": nbytes[name],
+            "device": {"min_ms": min(ds), "median_ms": statistics.median(ds), "max_ms": max(ds),
+                       "hbm_fraction_at_median": nbytes[name] / (statistics.median(ds) * 1e-3) / HBM_PEAK}}
+    batch.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
 
 
 if __name__ == "__main__":

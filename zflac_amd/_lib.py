@@ -38,6 +38,13 @@ class zflac_export_desc(ctypes.Structure):
                 ("channels", ctypes.c_uint16), ("frames", ctypes.c_uint64), ("starts", ctypes.POINTER(ctypes.c_uint64))]
 
 
+class zflac_resample_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("channels", ctypes.c_uint16), ("frames", ctypes.c_uint64), ("starts", ctypes.POINTER(ctypes.c_uint64)),
+                ("sample_rate", ctypes.c_uint32), ("zeros", ctypes.c_uint16), ("reserved", ctypes.c_uint16),
+                ("rolloff", ctypes.c_double), ("beta", ctypes.c_double)]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -63,6 +70,11 @@ SIGNATURES = {
     "zflac_hip_batch_export": (ctypes.c_int, [_P, ctypes.POINTER(zflac_export_desc), _P, ctypes.c_size_t,
                                               ctypes.POINTER(ctypes.c_uint64), _P]),
     "zflac_hip_batch_export_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
+    "zflac_hip_batch_export_resampled": (ctypes.c_int, [_P, ctypes.POINTER(zflac_resample_desc), _P, ctypes.c_size_t,
+                                                        ctypes.POINTER(ctypes.c_uint64), _P]),
+    "zflac_hip_resampled_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
+    "zflac_hip_batch_resample_tables": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64),
+                                                       ctypes.POINTER(ctypes.c_uint64)]),
     "zflac_hip_batch_size": (ctypes.c_size_t, [_P]),
     "zflac_hip_batch_destroy": (None, [_P]),
     "zflac_hip_error_name": (ctypes.c_char_p, [ctypes.c_int]),

@@ -13,9 +13,10 @@ LIB = os.path.join(HERE, "libzflac_hip.so")
 SOURCES = [os.path.join(CSRC, f"decode_k{k}_{lay}{mix}.hip") for k in (1, 2, 0) for lay in ("stereo", "mono", "multi")
            for mix in ("", "_mix")]
 SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip",
-                                            "stream_plan.cpp", "pipeline.cpp", "seq_planner.cpp", "md5_host.cpp", "abi.cpp")]
+                                            "resample.hip", "stream_plan.cpp", "resample_plan.cpp", "pipeline.cpp",
+                                            "seq_planner.cpp", "md5_host.cpp", "abi.cpp")]
 HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "device_common.h", "launch.h", "stream_plan.h",
-                                           "batch.h", "md5.hpp", "decode.inc")]
+                                           "resample_plan.h", "export_tile.h", "batch.h", "md5.hpp", "decode.inc")]
 DEPS = SOURCES + HEADERS + [os.path.join(ROOT, "include", "zflac_hip.h")]
 ARCH = os.environ.get("ZFLAC_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -101,7 +102,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
         cmd[1:1] = [f"-D{d}" for d in defines]
         if src.endswith(".hip"):
             cmd[1:1] = ["-x", "hip"]
-        if src.endswith("stream_plan.cpp"):  # the GPU-free planner: plain C++, no device pass
+        if src.endswith("_plan.cpp"):  # the GPU-free planners: plain C++, no device pass
             cmd[1:1] = ["-x", "c++"]
         if src.endswith("abi.cpp"):
             cmd[1:1] = [f'-DZFLAC_BUILD_ID="src={fp}"']

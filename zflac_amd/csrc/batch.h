@@ -14,6 +14,7 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "resample_plan.h"
 #include "stream_plan.h"
 
 namespace zflac {
@@ -49,6 +50,15 @@ struct DevBuf {
         ck(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
         n = count;
     }
+};
+
+// One polyphase tap table of a batch (zflac_hip_batch_export_resampled), kept in device memory
+// under the parameters it was built from.
+struct ResampleTable {
+    uint32_t fin = 0, fout = 0, zeros = 0;
+    double rolloff = 0, beta = 0;
+    ResampleRatio ratio;
+    DevBuf<float> taps;  // h[L][K]
 };
 
 struct StreamState : StreamPlan {  // the host parse (stream_plan.h), then:
@@ -253,17 +263,22 @@ struct zflac_batch {
     std::vector<uint32_t> pipe_who;
     uint32_t* pipe_pin = nullptr;
     zflac_timings timings = {};
-    // zflac_hip_batch_export: the per-row table goes through exp_pin (pinned) into exp_rows
-    // with an async copy on the export's stream. ev_exp_copy marks that copy (the next export
+    // zflac_hip_batch_export / _export_resampled: the per-row table (ExportRow or ResampleRow
+    // records, room for the larger) goes through exp_pin (pinned) into exp_rows with an async copy
+    // on the export's stream. ev_exp_copy marks that copy (the next export
     // waits for it on the host before it refills exp_pin), ev_exp the kernel (the next export's
     // stream waits for it before it overwrites exp_rows; while exp_pending, so do the next
     // run's streams before they overwrite the samples, and the destructor on the host).
-    zflac::ExportRow* exp_pin = nullptr;
-    zflac::DevBuf<zflac::ExportRow> exp_rows;
+    uint8_t* exp_pin = nullptr;
+    zflac::DevBuf<uint8_t> exp_rows;
     hipEvent_t ev_exp_copy = nullptr, ev_exp = nullptr;
     hipEvent_t ev_exp_t[2] = {};  // ZFLAC_FLAG_TIMING: around a synchronous export
     bool exp_any = false;      // ev_exp_copy / ev_exp have been recorded
     bool exp_pending = false;  // an export on a caller's stream may still read the samples
     double export_ms = -1;
+    // the resampled export's tap tables, one per distinct (source rate, target rate, zeros,
+    // rolloff, beta) met so far; a later export with the same parameters builds nothing
+    std::vector<std::unique_ptr<zflac::ResampleTable>> rs_tables;
+    uint64_t rs_built = 0;  // tables built over the batch's lifetime
     ~zflac_batch();  // abi.cpp
 };

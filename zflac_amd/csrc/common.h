@@ -278,4 +278,45 @@ struct ExportArgs {
     uint32_t vec;          // dst and its rows are 16-byte aligned: the 16-byte store paths apply
 };
 
+// k_resample (resample.hip): one row of the resampled dense destination. `e` is the row as
+// k_export sees it, with e.start and the window counted in frames of the RESAMPLED stream and
+// e.n_frames in frames of the source. taps == nullptr: the row is not filtered (its stream
+// already has the target rate, ended in an error, or the window lies past its end) and takes
+// k_export's paths on `e` as it stands. Otherwise output frame m is
+//   sum_k taps[((m * M) mod L) * K + k] * x[floor(m * M / L) - W + k]      (resample_plan.h)
+// and a workgroup takes `tile` output frames of the row, `cg` channels at a time (a frame's cg
+// channels lie side by side in LDS: one 4-, 8- or 16-byte read).
+struct ResampleRow {
+    ExportRow e;
+    const float* taps;  // h[L][K] in device memory
+    uint64_t n_out;     // frames of the resampled stream: ceil(e.n_frames * L / M)
+    uint32_t L, M;      // target rate / gcd, source rate / gcd
+    uint32_t W, K;      // half width and tap count, K = 2 W + 1
+    uint32_t tile;      // output frames per workgroup (resample_tile)
+    uint8_t cg;         // channels staged and summed together: 1, 2 or 4 (RESAMPLE_MAX_CG)
+    uint8_t tab_lds;    // the workgroup copies the table into LDS (else it reads taps from global memory)
+    uint8_t pad_[2];
+};
+static_assert(sizeof(ResampleRow) == 72, "ResampleRow is the 72-byte record host and kernel share");
+
+// LDS of a k_resample workgroup, in floats: 80 KiB, so that two workgroups (16 waves) share a CU's
+// 160 KiB.
+// A table of at most RESAMPLE_LDS_TABLE floats is kept there, in front of the staged input span,
+// which takes the rest (at least 14 KiB; all 80 KiB when the taps are read from global memory).
+constexpr uint32_t RESAMPLE_THREADS = 512;  // (the rows on k_export's paths use the first EXPORT_THREADS)
+constexpr uint32_t RESAMPLE_LDS_FLOATS = 20480;
+constexpr uint32_t RESAMPLE_LDS_TABLE = 16896;
+constexpr uint32_t RESAMPLE_MAX_TILE = 2048;  // output frames of a row per workgroup, at most
+constexpr uint32_t RESAMPLE_MAX_CG = 4;
+
+struct ResampleArgs {
+    const ResampleRow* rows;
+    void* dst;             // B x C x T elements of the export's dtype
+    uint64_t frames;       // T, in frames of the resampled streams
+    uint32_t channels;     // C
+    uint32_t n_rows;       // B
+    uint32_t tiles;        // workgroups per row: the most any row needs (ceil(T / its tile))
+    uint32_t vec;          // as ExportArgs::vec, for the rows on k_export's paths
+};
+
 }  // namespace zflac

@@ -44,4 +44,7 @@ hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode);
 // export.hip
 hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st);
 
+// resample.hip
+hipError_t launch_resample(int dtype, int layout, const ResampleArgs& a, hipStream_t st);
+
 }  // namespace zflac

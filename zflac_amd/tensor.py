@@ -1,4 +1,5 @@
-"""Decoded batches as dense torch tensors on the GPU (zflac_hip_batch_export, k_export).
+"""Decoded batches as dense torch tensors on the GPU (zflac_hip_batch_export, k_export; at one
+sample rate with sample_rate=: zflac_hip_batch_export_resampled, k_resample).
 
     import torch                      # before zflac_amd loads its library (see below)
     from zflac_amd import Batch, tensor
@@ -84,7 +85,8 @@ def check_single_runtime() -> None:
 
 
 def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.float32, layout="planar", out=None,
-           stream=None):
+           stream=None, sample_rate=None, resample_zeros=16, resample_rolloff=0.85,
+           resample_beta=8.555504641634386):
     """The last run of `batch` as one dense tensor -> (tensor, lengths).
 
     tensor: [B, channels, frames] (layout="planar") or [B, frames, channels] ("interleaved") of
@@ -94,10 +96,22 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
     an error are zero. lengths: int64 [B] on the same device, the valid frames of each row.
     frames defaults to the longest valid length, channels to the largest channel count of the OK
     streams. The export is enqueued on `stream` (default: torch's current stream of the device),
-    so torch work on that stream is ordered after it; nothing is synchronised."""
+    so torch work on that stream is ordered after it; nothing is synchronised.
+
+    sample_rate: every row resampled to this rate on the device (zflac_hip_batch_export_resampled,
+    k_resample: a Kaiser-windowed sinc of `resample_zeros` zero crossings a side, cutoff
+    `resample_rolloff` of the lower Nyquist rate, window shape `resample_beta`), so that streams of
+    any rates share one time base. frames, starts and lengths then count frames at sample_rate,
+    and dtype is a float type. A stream already at sample_rate is exported as without it."""
     check_single_runtime()
     if dtype not in _DTYPES:
         raise TypeError(f"dtype must be one of {sorted(map(str, _DTYPES))}")
+    if sample_rate is not None:
+        if dtype == torch.int32:
+            raise TypeError("a resampled export is float32, float16 or bfloat16")
+        sample_rate = int(sample_rate)
+        if not 1 <= sample_rate <= 1048575:
+            raise ValueError("1 <= sample_rate <= 1048575")
     if layout not in _LAYOUTS:
         raise ValueError("layout must be 'planar' or 'interleaved'")
     n = len(batch)
@@ -117,6 +131,8 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
             if rc or not inf.channels:
                 continue
             nf = inf.n_samples // inf.channels
+            if sample_rate is not None:
+                nf = batch._L.zflac_hip_resampled_frames(nf, inf.sample_rate, sample_rate)
             longest = max(longest, nf - (h_starts[i] if h_starts is not None else 0))
             widest = max(widest, inf.channels)
         frames = max(longest, 1) if frames is None else frames
@@ -142,11 +158,18 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
         # the null stream has no handle to pass: the library then exports on the batch's own
         # stream and returns when the tensor is complete; work queued on `out` goes first
         stream.synchronize()
-    desc = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), _DTYPES[dtype], _LAYOUTS[layout], channels,
-                                  frames, h_starts)
     valid = (ctypes.c_uint64 * max(n, 1))()
-    rc = batch._L.zflac_hip_batch_export(batch._h, ctypes.byref(desc), out.data_ptr() or None,
-                                         out.numel() * out.element_size(), valid, stream.cuda_stream or None)
+    if sample_rate is None:
+        desc = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), _DTYPES[dtype], _LAYOUTS[layout],
+                                      channels, frames, h_starts)
+        call = batch._L.zflac_hip_batch_export
+    else:
+        desc = _lib.zflac_resample_desc(ctypes.sizeof(_lib.zflac_resample_desc), _DTYPES[dtype], _LAYOUTS[layout],
+                                        channels, frames, h_starts, sample_rate, int(resample_zeros), 0,
+                                        float(resample_rolloff), float(resample_beta))
+        call = batch._L.zflac_hip_batch_export_resampled
+    rc = call(batch._h, ctypes.byref(desc), out.data_ptr() or None, out.numel() * out.element_size(), valid,
+              stream.cuda_stream or None)
     if n == 0 and rc == errors.InvalidArgument.code:
         rc = 0  # an empty tensor has no address to hand over
     errors.check(rc, "batch_export")
@@ -156,8 +179,9 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
 
 def decode_to_tensor(streams, device: int = 0, **kw):
     """Decode `streams` on `device` and export them -> (tensor, lengths, infos); infos[i] is
-    (error name, channels, sample_rate, bits_per_sample) of stream i. Keyword arguments as for
-    export(). The tensor is complete when this returns."""
+    (error name, channels, sample_rate, bits_per_sample) of stream i as decoded. Keyword arguments
+    as for export(): with sample_rate= every row of the tensor is at that rate. The tensor is
+    complete when this returns."""
     check_single_runtime()
     b = Batch(streams, device)
     try:
