@@ -175,6 +175,26 @@ const void *zflac_hip_batch_device_samples(zflac_batch *b, size_t i);
 int zflac_hip_batch_timings(zflac_batch *b, zflac_timings *t);
 int zflac_hip_batch_timings_ex(zflac_batch *b, zflac_timings *t, size_t size);
 #define ZFLAC_TIMINGS_V1_SIZE 80
+/* The k_decode kernels of the last completed run. Every frame group (the frames one decode wave
+ * takes: 64 / channels consecutive frames of the batch's streams of one container and channel
+ * count) is decoded by the kernel of its history bucket: the smallest of 4, 8, 12, 16, 32 that
+ * holds the highest predictor order among the group's subframes, or, when one of them is
+ * CONSTANT or VERBATIM, the MIX kernel of 8 or 32. *used: the OR, over the batch's classes, of
+ * the ZFLAC_BUCKET_* of every frame group as that run classified them. *planned: the buckets
+ * that had a launch of their own when the run was enqueued (predicted at creation from each
+ * stream's first subframe, plus what earlier runs found); groups of a bucket in used & ~planned
+ * were decoded by the run's `rest` launch (zflac_timings.rest_launches), and the bucket is
+ * planned from the next run on. ZFLAC_E_INVALID_ARGUMENT: a NULL batch or pointer, before the
+ * first completed run, between _submit and _wait. */
+#define ZFLAC_BUCKET_8 1u
+#define ZFLAC_BUCKET_4 2u
+#define ZFLAC_BUCKET_16 4u
+#define ZFLAC_BUCKET_32 8u
+#define ZFLAC_BUCKET_MIX_8 16u
+#define ZFLAC_BUCKET_MIX_32 32u
+#define ZFLAC_BUCKET_12 64u
+#define ZFLAC_BUCKET_ALL 127u
+int zflac_hip_batch_decode_buckets(zflac_batch *b, uint32_t *used, uint32_t *planned);
 size_t zflac_hip_batch_size(zflac_batch *b);
 void zflac_hip_batch_destroy(zflac_batch *b);
 
@@ -304,7 +324,7 @@ const char *zflac_hip_build_id(void);
  *    Added without a bump (no existing struct or signature changed): zflac_export_desc,
  *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*;
  *    zflac_resample_desc, zflac_hip_batch_export_resampled, zflac_hip_resampled_frames,
- *    zflac_hip_batch_resample_tables. */
+ *    zflac_hip_batch_resample_tables; zflac_hip_batch_decode_buckets, ZFLAC_BUCKET_*. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

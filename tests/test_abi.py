@@ -63,8 +63,28 @@ def test_invalid_arguments():
     assert L.zflac_hip_batch_info(None, 0, None) == 14
     assert L.zflac_hip_batch_read(None, 0, None, 0, 0) == 14
     assert L.zflac_hip_batch_size(None) == 0
+    used, planned = ctypes.c_uint32(), ctypes.c_uint32()
+    assert L.zflac_hip_batch_decode_buckets(None, ctypes.byref(used), ctypes.byref(planned)) == 14
+    assert L.zflac_hip_batch_decode_buckets(None, None, None) == 14
     L.zflac_hip_batch_destroy(None)
     L.zflac_hip_close(None)
+
+
+def test_decode_buckets_symbol_and_constants():
+    """zflac_hip_batch_decode_buckets is declared, exported and bound, and the header's
+    ZFLAC_BUCKET_* are the values the binding carries (the library itself static_asserts them
+    against bucket_bit() of common.h): seven distinct bits that make up ZFLAC_BUCKET_ALL."""
+    L = _lib.load()
+    assert "zflac_hip_batch_decode_buckets" in _header_functions()
+    assert hasattr(L, "zflac_hip_batch_decode_buckets")
+    text = open(os.path.join(ROOT, "include", "zflac_hip.h")).read()
+    hdr = {n: int(v) for n, v in re.findall(r"#define ZFLAC_BUCKET_(\w+) (\d+)u", text)}
+    names = ["8", "4", "16", "32", "MIX_8", "MIX_32", "12"]
+    assert sorted(hdr) == sorted(names + ["ALL"])
+    assert hdr == {n: getattr(_lib, "BUCKET_" + n) for n in hdr}
+    assert [hdr[n] for n in names] == [1, 2, 4, 8, 16, 32, 64]
+    assert hdr["ALL"] == sum(hdr[n] for n in names)
+    assert re.search(r"Added without a bump.*zflac_hip_batch_decode_buckets", text, re.S)
 
 
 def test_kernels_compiled_for_gfx950():

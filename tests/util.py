@@ -135,21 +135,36 @@ def splice_frames(a, b, k: int) -> bytes:
     depth, block size, rate, frame count), under `a`'s metadata with the STREAMINFO MD5 of
     the spliced PCM. zflac does not check frame numbers, so this is a valid stream whose
     frames change predictor between the two parts."""
+    return splice_many([a, b], [k])[0]
+
+
+def splice_many(streams, cuts):
+    """splice_frames for several parts: frames [cuts[i-1], cuts[i]) of streams[i] (cuts[-1] = 0,
+    the last part runs to the end), under the first stream's metadata with the STREAMINFO MD5
+    of the spliced PCM. The streams share channels, depth, block size, rate and frame count, and
+    every frame before the last cut is a full block. Returns (flac bytes, spliced source PCM)."""
     import hashlib
 
-    ao = [int(x) for x in a.frame_offsets] + [len(a.flac)]
-    bo = [int(x) for x in b.frame_offsets] + [len(b.flac)]
-    assert len(ao) == len(bo)
-    data = bytearray(a.flac[:ao[k]] + b.flac[bo[k]:])
-    bps, ch = a.config["bps"], a.config["channels"]
-    per = a.pcm.size // (len(ao) - 1)  # interleaved samples per (full) frame
-    pcm = np.concatenate([a.pcm[:k * per], b.pcm[k * per:]])
-    dt = container_dtype(bps)
+    a = streams[0]
+    assert len(cuts) == len(streams) - 1 and list(cuts) == sorted(cuts)
+    bps, ch, bs = a.config["bps"], a.config["channels"], a.config["block_size"]
+    n = len(a.frame_offsets)
+    edges = [0] + [int(c) for c in cuts] + [n]
+    data, pcm = bytearray(a.flac[:a.frames_begin]), []
+    for s, lo, hi in zip(streams, edges, edges[1:]):
+        assert (s.config["bps"], s.config["channels"], s.config["block_size"]) == (bps, ch, bs)
+        assert len(s.frame_offsets) == n and s.pcm.size == a.pcm.size and s.frames_begin == a.frames_begin
+        so = [int(x) for x in s.frame_offsets] + [len(s.flac)]
+        data += s.flac[so[lo]:so[hi]]
+        pcm.append(s.pcm[lo * bs * ch:(hi * bs * ch if hi < n else s.pcm.size)])
+    pcm = np.concatenate(pcm)
     if (bps + 7) // 8 * 8 == 24:
         msg = np.ascontiguousarray(pcm.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :3]).tobytes()
     else:
-        msg = pcm.astype(np.dtype(dt).newbyteorder("<")).tobytes()
-    assert ch == b.config["channels"]
-    o = streaminfo_offset(bytes(data)) + 18
-    data[o:o + 16] = hashlib.md5(msg).digest()
-    return bytes(data)
+        msg = pcm.astype(np.dtype(container_dtype(bps)).newbyteorder("<")).tobytes()
+    o = streaminfo_offset(bytes(data))
+    if len(streams) > 2:  # STREAMINFO's frame-size range over every source (two parts keep the first's)
+        data[o + 4:o + 7] = min(int.from_bytes(s.flac[o + 4:o + 7], "big") for s in streams).to_bytes(3, "big")
+        data[o + 7:o + 10] = max(int.from_bytes(s.flac[o + 7:o + 10], "big") for s in streams).to_bytes(3, "big")
+    data[o + 18:o + 34] = hashlib.md5(msg).digest()
+    return bytes(data), pcm

@@ -75,6 +75,8 @@ SIGNATURES = {
     "zflac_hip_resampled_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "zflac_hip_batch_resample_tables": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64),
                                                        ctypes.POINTER(ctypes.c_uint64)]),
+    "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
+                                                      ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_size": (ctypes.c_size_t, [_P]),
     "zflac_hip_batch_destroy": (None, [_P]),
     "zflac_hip_error_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -96,6 +98,15 @@ EXPORT_BF16 = 2
 EXPORT_I32 = 3
 LAYOUT_PLANAR = 0
 LAYOUT_INTERLEAVED = 1
+# zflac_hip_batch_decode_buckets: one bit per k_decode history bucket (ZFLAC_BUCKET_*)
+BUCKET_8 = 1
+BUCKET_4 = 2
+BUCKET_16 = 4
+BUCKET_32 = 8
+BUCKET_MIX_8 = 16
+BUCKET_MIX_32 = 32
+BUCKET_12 = 64
+BUCKET_ALL = 127
 
 _lib = None
 

@@ -180,6 +180,15 @@ class Batch:
         rc = self._L.zflac_hip_batch_timings_ex(self._h, ctypes.byref(t), ctypes.sizeof(t))
         return None if rc else t
 
+    def decode_buckets(self):
+        """(used, planned) of the last completed run (zflac_hip_batch_decode_buckets): the
+        _lib.BUCKET_* of the k_decode kernels its frame groups were classified into, and of
+        the launches the run was enqueued with."""
+        used, planned = ctypes.c_uint32(), ctypes.c_uint32()
+        errors.check(self._L.zflac_hip_batch_decode_buckets(self._h, ctypes.byref(used), ctypes.byref(planned)),
+                     "batch_decode_buckets")
+        return used.value, planned.value
+
     def device_samples(self, i: int) -> int:
         return self._L.zflac_hip_batch_device_samples(self._h, i) or 0
 

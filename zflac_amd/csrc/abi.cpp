@@ -511,6 +511,19 @@ int zflac_hip_batch_resample_tables(zflac_batch* b, uint64_t* built, uint64_t* h
     return E_OK;
 }
 
+static_assert(ZFLAC_BUCKET_8 == bucket_bit(8, false) && ZFLAC_BUCKET_4 == bucket_bit(4, false) &&
+                  ZFLAC_BUCKET_16 == bucket_bit(16, false) && ZFLAC_BUCKET_32 == bucket_bit(32, false) &&
+                  ZFLAC_BUCKET_MIX_8 == bucket_bit(8, true) && ZFLAC_BUCKET_MIX_32 == bucket_bit(32, true) &&
+                  ZFLAC_BUCKET_12 == bucket_bit(12, false) && ZFLAC_BUCKET_ALL == BUCKET_MASK_ALL,
+              "ZFLAC_BUCKET_* (zflac_hip.h) and bucket_bit() (common.h) disagree");
+
+int zflac_hip_batch_decode_buckets(zflac_batch* b, uint32_t* used, uint32_t* planned) {
+    if (!b || !used || !planned || !b->ran || b->submitted) return E_INVALID_ARGUMENT;
+    *used = b->buckets_used;
+    *planned = b->buckets_planned;
+    return E_OK;
+}
+
 int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
     if (!b || !ms || b->export_ms < 0) return E_INVALID_ARGUMENT;
     *ms = b->export_ms;

@@ -280,5 +280,8 @@ struct zflac_batch {
     // rolloff, beta) met so far; a later export with the same parameters builds nothing
     std::vector<std::unique_ptr<zflac::ResampleTable>> rs_tables;
     uint64_t rs_built = 0;  // tables built over the batch's lifetime
+    // zflac_hip_batch_decode_buckets: over the classes, the buckets the last completed run's
+    // classification found (h_misc[2]) and the launch plan (full_mask) that run was enqueued with
+    uint32_t buckets_used = 0, buckets_planned = 0;
     ~zflac_batch();  // abi.cpp
 };

@@ -534,9 +534,10 @@ void finish_batch(zflac_batch* b) {
         }
         ck(hipEventSynchronize(b->ev_md5));
     }
-    uint32_t rest_launches = 0, sequential = 0;
+    uint32_t rest_launches = 0, sequential = 0, used = 0, planned = 0;
     for (size_t ci = 0; ci < b->classes.size(); ci++) {
         Class& C = *b->classes[ci];
+        planned |= C.full_mask;  // (only this function changes it, below)
         for (int attempt = 0; attempt < 3; attempt++) {
             if (!C.h_misc[1] && C.h_misc[0] <= C.cap) break;
             C.cap = std::max<uint32_t>(C.h_misc[0] + 1024, C.cap * 2);  // candidate table overflow: grow, redo
@@ -549,6 +550,7 @@ void finish_batch(zflac_batch* b) {
         // more candidates than the grids were sized for (false syncs): correct (the kernels
         // stride over them), but slower; size the next run's grids for them
         if (C.h_misc[0] > C.grid_frames) C.grid_frames = std::min(C.cap, C.h_misc[0] + C.h_misc[0] / 64 + 64);
+        used |= C.h_misc[2] & BUCKET_MASK_ALL;
         if (C.full_mask && (C.h_misc[2] & ~C.full_mask)) {  // a bucket without a launch was used
             enqueue_rest(b, C);
             C.redone = true;
@@ -655,6 +657,8 @@ void finish_batch(zflac_batch* b) {
     b->timings.samples = samples;
     b->timings.rest_launches = rest_launches;
     b->timings.sequential_streams = sequential;
+    b->buckets_used = used;
+    b->buckets_planned = planned;
 }
 
 int create_batch(const zflac_stream* streams, size_t n, int device, int flags, zflac_batch** out) {
