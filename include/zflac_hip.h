@@ -195,6 +195,17 @@ int zflac_hip_batch_timings_ex(zflac_batch *b, zflac_timings *t, size_t size);
 #define ZFLAC_BUCKET_12 64u
 #define ZFLAC_BUCKET_ALL 127u
 int zflac_hip_batch_decode_buckets(zflac_batch *b, uint32_t *used, uint32_t *planned);
+/* What built the frame table of the last completed run. The streams of one container and channel
+ * count (a class) share a table, found either by k_scan (every input byte searched for frame sync
+ * codes) or by k_hop (from each frame header to the next, by the frame number: classes of many
+ * short streams with fixed blocking and a STREAMINFO total, see ZFLAC_FLAG_FRONT_*). *planned: the
+ * OR, over the batch's classes, of the ZFLAC_FRONT_* each class's run was enqueued with. *used: the
+ * same for the table the results came from; a class whose hop lost a stream is redone with the
+ * scan front by _wait (planned HOP, used SCAN) and keeps the scan front in later runs. Results
+ * never depend on the front. ZFLAC_E_INVALID_ARGUMENT as for _decode_buckets. */
+#define ZFLAC_FRONT_SCAN 1
+#define ZFLAC_FRONT_HOP 2
+int zflac_hip_batch_front(zflac_batch *b, int *planned, int *used);
 size_t zflac_hip_batch_size(zflac_batch *b);
 void zflac_hip_batch_destroy(zflac_batch *b);
 
@@ -306,6 +317,19 @@ int zflac_hip_batch_resample_tables(zflac_batch *b, uint64_t *built, uint64_t *h
  * otherwise. These force one (testing, timing); results are identical. */
 #define ZFLAC_FLAG_WALK_LANE 16
 #define ZFLAC_FLAG_WALK_WAVE 32
+/* The frame-table front (zflac_hip_batch_front). By default (and with both flags) each class
+ * takes k_hop when every stream has a STREAMINFO total and fixed blocking (first frame 0xF8,
+ * STREAMINFO min block == max block), no stream has more than 64 frames and the class has at
+ * least 768 streams; k_scan otherwise. _FRONT_SCAN forces k_scan; _FRONT_HOP forces k_hop for
+ * every class whose streams allow it (totals, fixed blocking, frames per stream), whatever the
+ * stream count. The environment variable ZFLAC_FRONT=scan|hop|auto does the same for batches
+ * created without either flag. ZFLAC_HOP_MAX_FRAMES and ZFLAC_HOP_MIN_STREAMS, read when a batch
+ * is created, replace the two limits: overrides for tests and for the sweeps the limits were
+ * measured with (tools/sweep_front.py), not tuning knobs. k_hop also requires every frame but a
+ * stream's last to code the STREAMINFO block size; a stream that does not sends its class back to
+ * k_scan like any stream the hop cannot follow. Results are identical. */
+#define ZFLAC_FLAG_FRONT_SCAN 64
+#define ZFLAC_FLAG_FRONT_HOP 128
 
 const char *zflac_hip_error_name(int code);
 /* Number of HIP devices visible; 0 means every decode will fail with ZFLAC_E_DEVICE. */
@@ -324,7 +348,8 @@ const char *zflac_hip_build_id(void);
  *    Added without a bump (no existing struct or signature changed): zflac_export_desc,
  *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*;
  *    zflac_resample_desc, zflac_hip_batch_export_resampled, zflac_hip_resampled_frames,
- *    zflac_hip_batch_resample_tables; zflac_hip_batch_decode_buckets, ZFLAC_BUCKET_*. */
+ *    zflac_hip_batch_resample_tables; zflac_hip_batch_decode_buckets, ZFLAC_BUCKET_*;
+ *    zflac_hip_batch_front, ZFLAC_FRONT_*, ZFLAC_FLAG_FRONT_*. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -27,7 +27,7 @@ fn = L.zflac_hip_replay
 fn.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                ctypes.POINTER(ctypes.c_double)]
 arr = (ctypes.c_void_p * nb)(*[b._h.value if hasattr(b._h, "value") else b._h for b in bs])
-out = {"inflight": nb, "reps": reps}
+out = {"inflight": nb, "reps": reps, "build_id": zflac_amd.build_id(), "front_env": os.environ.get("ZFLAC_FRONT", "auto")}
 parts = ((1, "walk"), (2, "decode"), (3, "walk+decode"), (4, "run"), (8, "scan"), (16, "front"))
 only = os.environ.get("REPLAY_PARTS")  # e.g. "scan,front3"
 for what, name in parts:

@@ -77,6 +77,7 @@ SIGNATURES = {
                                                        ctypes.POINTER(ctypes.c_uint64)]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
+    "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "zflac_hip_batch_size": (ctypes.c_size_t, [_P]),
     "zflac_hip_batch_destroy": (None, [_P]),
     "zflac_hip_error_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -91,6 +92,8 @@ FLAG_DEVICE_MD5 = 4
 FLAG_CHECK_CRC16 = 8  # beyond zflac (src/zflac.zig:548-551 ignores the trailer)
 FLAG_WALK_LANE = 16
 FLAG_WALK_WAVE = 32
+FLAG_FRONT_SCAN = 64  # force the frame-table front of every class: k_scan ...
+FLAG_FRONT_HOP = 128  # ... or k_hop (where the streams allow it)
 # zflac_hip_batch_export: element type and layout of the dense tensor
 EXPORT_F32 = 0
 EXPORT_F16 = 1
@@ -107,6 +110,9 @@ BUCKET_MIX_8 = 16
 BUCKET_MIX_32 = 32
 BUCKET_12 = 64
 BUCKET_ALL = 127
+# zflac_hip_batch_front: what built the frame table (ZFLAC_FRONT_*), ORed over the batch's classes
+FRONT_SCAN = 1
+FRONT_HOP = 2
 
 _lib = None
 

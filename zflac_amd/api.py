@@ -113,7 +113,8 @@ class Batch:
     """
 
     def __init__(self, streams, device: int = 0, timing: bool = False, force_slow: bool = False,
-                 device_md5: bool = False, check_crc16: bool = False, walk: str | None = None):
+                 device_md5: bool = False, check_crc16: bool = False, walk: str | None = None,
+                 front: str | None = None):
         self._L = _lib.load()
         self.device = device
         self._bufs = [bytes(s) for s in streams]
@@ -126,7 +127,8 @@ class Batch:
             arr[i].len = len(b)
         flags = ((_lib.FLAG_TIMING if timing else 0) | (_lib.FLAG_FORCE_SLOW if force_slow else 0)
                  | (_lib.FLAG_DEVICE_MD5 if device_md5 else 0) | (_lib.FLAG_CHECK_CRC16 if check_crc16 else 0)
-                 | {None: 0, "lane": _lib.FLAG_WALK_LANE, "wave": _lib.FLAG_WALK_WAVE}[walk])
+                 | {None: 0, "lane": _lib.FLAG_WALK_LANE, "wave": _lib.FLAG_WALK_WAVE}[walk]
+                 | {None: 0, "auto": 0, "scan": _lib.FLAG_FRONT_SCAN, "hop": _lib.FLAG_FRONT_HOP}[front])
         self._h = ctypes.c_void_p()
         rc = self._L.zflac_hip_batch_create(arr, len(self._bufs), device, flags, ctypes.byref(self._h))
         self._keep = None  # the library copied the bytes to HBM
@@ -188,6 +190,14 @@ class Batch:
         errors.check(self._L.zflac_hip_batch_decode_buckets(self._h, ctypes.byref(used), ctypes.byref(planned)),
                      "batch_decode_buckets")
         return used.value, planned.value
+
+    def front(self):
+        """(planned, used) of the last completed run (zflac_hip_batch_front): _lib.FRONT_SCAN /
+        _lib.FRONT_HOP, ORed over the batch's classes: the front each class's run was enqueued
+        with, and the one its accepted frame table came from."""
+        planned, used = ctypes.c_int(), ctypes.c_int()
+        errors.check(self._L.zflac_hip_batch_front(self._h, ctypes.byref(planned), ctypes.byref(used)), "batch_front")
+        return planned.value, used.value
 
     def device_samples(self, i: int) -> int:
         return self._L.zflac_hip_batch_device_samples(self._h, i) or 0

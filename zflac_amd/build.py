@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzflac_hip.so")
 SOURCES = [os.path.join(CSRC, f"decode_k{k}_{lay}{mix}.hip") for k in (1, 2, 0) for lay in ("stereo", "mono", "multi")
            for mix in ("", "_mix")]
-SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip",
+SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "hop.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip",
                                             "resample.hip", "stream_plan.cpp", "resample_plan.cpp", "pipeline.cpp",
                                             "seq_planner.cpp", "md5_host.cpp", "abi.cpp")]
 HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "device_common.h", "launch.h", "stream_plan.h",

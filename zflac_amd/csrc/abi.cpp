@@ -524,6 +524,16 @@ int zflac_hip_batch_decode_buckets(zflac_batch* b, uint32_t* used, uint32_t* pla
     return E_OK;
 }
 
+static_assert(ZFLAC_FRONT_SCAN == FRONT_SCAN && ZFLAC_FRONT_HOP == FRONT_HOP,
+              "ZFLAC_FRONT_* (zflac_hip.h) and Front (stream_plan.h) disagree");
+
+int zflac_hip_batch_front(zflac_batch* b, int* planned, int* used) {
+    if (!b || !planned || !used || !b->ran || b->submitted) return E_INVALID_ARGUMENT;
+    *planned = b->front_planned;
+    *used = b->front_used;
+    return E_OK;
+}
+
 int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
     if (!b || !ms || b->export_ms < 0) return E_INVALID_ARGUMENT;
     *ms = b->export_ms;
@@ -564,6 +574,10 @@ extern "C" int zflac_hip_replay(zflac_batch** bs, int nb, int reps, int what, do
                 Class& C = *b->classes[0];
                 if (what == 4) {
                     enqueue_class(b, C, false, false);
+                    continue;
+                }
+                if (what >= 8 && C.front == FRONT_HOP) {  // the front alone: k_hop
+                    ck(launch_hop(hop_args(C), b->rs));
                     continue;
                 }
                 if (what >= 8) {  // the front alone: 8 k_scan, 16 k_scan + k_scan_chunks + k_compact

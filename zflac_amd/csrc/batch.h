@@ -90,6 +90,15 @@ struct Class {
     // the first subframe of each member's first frame, at batch creation (plan_buckets)
     uint32_t full_mask = 0;
     bool redone = false;  // the last run re-ran the class (candidate table regrown)
+    // The front that builds the frame table: k_scan + k_scan_chunks + k_compact, or k_hop
+    // (plan_hop, stream_plan.h). A run whose hop lost a stream (h_misc[3] == hop_epoch) is redone
+    // with the scan front by finish_batch, and the class keeps the scan front from then on.
+    Front front = FRONT_SCAN;     // of the next run
+    Front front_run = FRONT_SCAN, front_used = FRONT_SCAN;  // of the last run: enqueued with / results from
+    std::vector<HopDesc> hop;
+    DevBuf<HopDesc> d_hop;
+    uint32_t hop_frames = 0;  // sum of the streams' frame counts
+    uint32_t hop_epoch = 0;   // HopArgs::epoch of the last hop run
     DevBuf<uint8_t> in;
     DevBuf<uint8_t> out;
     DevBuf<StreamDesc> d_desc;
@@ -201,6 +210,7 @@ void finish_md5(zflac_batch* b, bool timing);
 DecodeArgs decode_args(Class& C);
 ScanArgs scan_args(Class& C);
 CompactArgs compact_args(Class& C);
+HopArgs hop_args(Class& C);  // (a new epoch each call)
 // k_walk or k_walk_wave (subframe start offsets, 2+ channels) then k_decode; `mid`
 // (optional) is recorded between the two launches. With a `front` stream the walk runs
 // there and k_decode waits for it on `st` through the event `join`. `est_frames`: the
@@ -283,5 +293,8 @@ struct zflac_batch {
     // zflac_hip_batch_decode_buckets: over the classes, the buckets the last completed run's
     // classification found (h_misc[2]) and the launch plan (full_mask) that run was enqueued with
     uint32_t buckets_used = 0, buckets_planned = 0;
+    // zflac_hip_batch_front: over the classes, the fronts the last completed run was enqueued
+    // with and the ones its frame tables came from (ZFLAC_FRONT_*)
+    int front_planned = 0, front_used = 0;
     ~zflac_batch();  // abi.cpp
 };

@@ -105,6 +105,43 @@ struct ScanArgs {
     uint32_t* misc;
 };
 
+// k_hop (hop.hip): the frame table of a class of many short fixed-blocking streams with known
+// totals, found by hopping from header to header (one entry per stream, beside StreamDesc).
+struct HopDesc {
+    uint32_t n_frames;  // ceil(total / block): the frames zflac reads (src/zflac.zig:341)
+    uint32_t f0;        // the stream's first index in the class's frame table
+    uint32_t units;     // block size * channels: output elements of every frame but the last
+    uint32_t guess;     // the first hop's size guess: frame bytes / n_frames
+};
+static_assert(sizeof(HopDesc) == 16, "HopDesc is the 16-byte record host and kernel share");
+
+// A class takes the hop front when every stream has at most HOP_MAX_FRAMES frames and the class
+// at least HOP_MIN_STREAMS streams (stream_plan.h: plan_hop); measured, DESIGN.md §5.3.
+#ifndef ZFLAC_HOP_MAX_FRAMES
+#define ZFLAC_HOP_MAX_FRAMES 64
+#endif
+#ifndef ZFLAC_HOP_MIN_STREAMS
+#define ZFLAC_HOP_MIN_STREAMS 768
+#endif
+constexpr uint32_t HOP_MAX_FRAMES = ZFLAC_HOP_MAX_FRAMES;
+constexpr uint32_t HOP_MIN_STREAMS = ZFLAC_HOP_MIN_STREAMS;
+
+struct HopArgs {
+    const uint8_t* in;
+    const StreamDesc* streams;
+    const HopDesc* hop;
+    uint32_t n_streams;
+    uint32_t total_frames;  // sum of n_frames: the run's frame count, written to misc[0]
+    uint32_t cap;           // candidate table capacity
+    uint32_t epoch;         // nonzero, new for every run: misc[3] == epoch means a hop of this run failed
+    uint64_t* c_pos;
+    uint32_t* c_stream;
+    uint64_t* c_out;
+    uint32_t* chunk_off;    // [first_chunk] and [end_chunk] of every stream: its table range (k_verify)
+    uint32_t* status;       // per stream: 0, or 2 where the hop failed
+    uint32_t* misc;         // the run's 4 counters: [0] frames, [1] overflow = 0, [2] buckets = 0, [3] see epoch
+};
+
 struct CompactArgs {
     const uint8_t* in;
     const StreamDesc* streams;

@@ -211,4 +211,31 @@ ZFLAC_HDI FrameHdr parse_frame_header_t(At&& at, uint64_t avail, uint32_t si_rat
     return h;
 }
 
+// The value of the header's coded number (read_coded_number, src/zflac.zig:203-214; header
+// byte 4 onwards), which parse_frame_header_t only skips: the frame number of a fixed-blocking
+// stream, the first sample's number of a variable-blocking one. False where zflac's reader
+// fails (InvalidCodedNumber, or fewer than `avail` bytes). `at` as for parse_frame_header_t.
+template <typename At>
+ZFLAC_HDI bool coded_number_value(At&& at, uint64_t avail, uint64_t& value) {
+    value = 0;
+    if (avail <= 4) return false;
+    const uint32_t first = at(4);
+    uint32_t ones = 0;
+    ZFLAC_UNROLL
+    for (int k = 0; k < 8; k++)
+        if (ones == (uint32_t)k && (first & (0x80u >> k))) ones++;
+    if (first == 0xFF || ones == 1) return false;
+    if (ones == 0) {
+        value = first;
+        return true;
+    }
+    if (avail < (uint64_t)4 + ones) return false;
+    uint64_t v = first & (0x7Fu >> ones);
+    ZFLAC_UNROLL
+    for (uint32_t k = 1; k < 7; k++)
+        if (k < ones) v = (v << 6) | (at(4 + k) & 0x3Fu);
+    value = v;
+    return true;
+}
+
 }  // namespace zflac

@@ -18,6 +18,9 @@ hipError_t launch_compact(const CompactArgs& a, hipStream_t st);
 hipError_t launch_sync_list(const SyncListArgs& a, hipStream_t st);
 hipError_t launch_verify(const VerifyArgs& a, uint32_t max_items, hipStream_t st);
 
+// hop.hip: the frame table in place of launch_scan + launch_scan_chunks + launch_compact
+hipError_t launch_hop(const HopArgs& a, hipStream_t st);
+
 // decode_k{0,1,2}_{stereo,mono,multi}.hip: the bucket launches of one (container kind, layout);
 // each ends with its _mix unit's (constant / verbatim subframes). launch_walk_k*: k_walk of the
 // container (defined in the stereo unit).

@@ -122,6 +122,8 @@ void prescan_unknown_totals(zflac_batch* b, Class& C, std::vector<uint64_t>& uni
     }
 }
 
+void plan_front(zflac_batch* b, Class& C);  // below
+
 void alloc_class(zflac_batch* b, Class& C, const zflac_stream* src) {
     C.full_mask = plan_buckets(b, C, src);
     const int esz = esz_of_kind(C.kind);
@@ -194,6 +196,8 @@ void alloc_class(zflac_batch* b, Class& C, const zflac_stream* src) {
     C.chunk_off.alloc(nc + 1);
     C.chunk_uoff.alloc(nc + 1);
     C.misc.alloc(4 + C.members.size());
+    // (misc[3], k_hop's hop_failed mark, is compared with the run's epoch and zeroed by no hop run)
+    ck(hipMemset(C.misc.p, 0, (4 + C.members.size()) * sizeof(uint32_t)));
     C.status = C.misc.p + 4;
     C.dummy.alloc(DUMMY_BYTES + PROBE_BYTES);
     if (C.any_unknown) {  // reservations of the streams without a STREAMINFO total
@@ -268,6 +272,37 @@ void alloc_class(zflac_batch* b, Class& C, const zflac_stream* src) {
     C.cap = (uint32_t)std::min<uint64_t>(est_frames + C.chunks.size() * 2 + 1024, 0x7FFFFFFFull);
     C.est_frames = est_frames;
     C.grid_frames = (uint32_t)std::min<uint64_t>(grid_frames + grid_frames / 64 + 64, C.cap);
+    plan_front(b, C);
+}
+
+// ZFLAC_FRONT=scan|hop|auto for batches created without ZFLAC_FLAG_FRONT_*; ZFLAC_HOP_MAX_FRAMES /
+// ZFLAC_HOP_MIN_STREAMS replace the compiled limits (the sweeps they were measured with, tests).
+FrontMode front_mode(int flags) {
+    const int f = flags & (ZFLAC_FLAG_FRONT_SCAN | ZFLAC_FLAG_FRONT_HOP);
+    if (f == ZFLAC_FLAG_FRONT_SCAN) return FRONT_FORCE_SCAN;
+    if (f == ZFLAC_FLAG_FRONT_HOP) return FRONT_FORCE_HOP;
+    if (f) return FRONT_AUTO;
+    const char* e = std::getenv("ZFLAC_FRONT");
+    return !e ? FRONT_AUTO : (e[0] == 's' ? FRONT_FORCE_SCAN : (e[0] == 'h' ? FRONT_FORCE_HOP : FRONT_AUTO));
+}
+
+void plan_front(zflac_batch* b, Class& C) {
+    HopLimits lim;
+    if (const char* e = std::getenv("ZFLAC_HOP_MAX_FRAMES")) lim.max_frames = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char* e = std::getenv("ZFLAC_HOP_MIN_STREAMS")) lim.min_streams = (uint32_t)std::strtoul(e, nullptr, 10);
+    std::vector<const StreamPlan*> plans(C.members.size());
+    for (size_t m = 0; m < C.members.size(); m++) plans[m] = &b->streams[C.members[m]];
+    C.hop.resize(C.members.size());
+    uint64_t total = 0;
+    C.front = plan_hop(plans.data(), plans.size(), front_mode(b->flags), lim, C.hop.data(), &total);
+    if (C.front == FRONT_HOP && total > C.cap) C.front = FRONT_SCAN;  // (cap >= the exact count: never)
+    if (C.front != FRONT_HOP) {
+        C.hop.clear();
+        return;
+    }
+    C.hop_frames = (uint32_t)total;
+    C.d_hop.alloc(C.hop.size());
+    ck(hipMemcpy(C.d_hop.p, C.hop.data(), C.hop.size() * sizeof(HopDesc), hipMemcpyHostToDevice));
 }
 
 void alloc_candidates(Class& C) {
@@ -320,6 +355,26 @@ CompactArgs compact_args(Class& C) {
     a.c_stream = C.c_stream.p;
     a.c_out = C.c_out.p;
     a.overflow = C.misc.p + 1;
+    return a;
+}
+
+HopArgs hop_args(Class& C) {
+    HopArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.in = C.in.p;
+    a.streams = C.d_desc.p;
+    a.hop = C.d_hop.p;
+    a.n_streams = (uint32_t)C.members.size();
+    a.total_frames = C.hop_frames;
+    a.cap = C.cap;
+    if (++C.hop_epoch == 0) C.hop_epoch = 1;
+    a.epoch = C.hop_epoch;
+    a.c_pos = C.c_pos.p;
+    a.c_stream = C.c_stream.p;
+    a.c_out = C.c_out.p;
+    a.chunk_off = C.chunk_off.p;
+    a.status = C.status;
+    a.misc = C.misc.p;
     return a;
 }
 
@@ -441,9 +496,14 @@ void enqueue_class(zflac_batch* b, Class& C, bool timing_first, bool timing_last
     if (nch == 0)  // (k_scan zeroes them otherwise)
         ck(hipMemsetAsync(C.misc.p, 0, (4 + C.members.size()) * sizeof(uint32_t), st));
     if (timing_first) ck(hipEventRecord(b->ev[0], st));
-    ck(launch_scan(scan_args(C), st));
-    if (nch) ck(launch_scan_chunks(C.chunk_cnt.p, C.chunk_units.p, nch, C.chunk_off.p, C.chunk_uoff.p, C.misc.p, st));
-    ck(launch_compact(compact_args(C), st));
+    C.front_run = C.front;
+    if (C.front == FRONT_HOP) {  // the frame table by hopping from header to header: one launch
+        ck(launch_hop(hop_args(C), st));
+    } else {
+        ck(launch_scan(scan_args(C), st));
+        if (nch) ck(launch_scan_chunks(C.chunk_cnt.p, C.chunk_units.p, nch, C.chunk_off.p, C.chunk_uoff.p, C.misc.p, st));
+        ck(launch_compact(compact_args(C), st));
+    }
     if (timing_last) ck(hipEventRecord(b->ev[1], st));
     DecodeArgs da = decode_args(C);
     da.bucket_used = C.misc.p + 2;
@@ -535,9 +595,21 @@ void finish_batch(zflac_batch* b) {
         ck(hipEventSynchronize(b->ev_md5));
     }
     uint32_t rest_launches = 0, sequential = 0, used = 0, planned = 0;
+    b->front_planned = b->front_used = 0;
     for (size_t ci = 0; ci < b->classes.size(); ci++) {
         Class& C = *b->classes[ci];
         planned |= C.full_mask;  // (only this function changes it, below)
+        b->front_planned |= C.front_run;
+        C.front_used = C.front_run;
+        if (C.front_run == FRONT_HOP && C.h_misc[3] == C.hop_epoch) {
+            // the hop lost a stream (numbers out of sequence, a size jump beyond its probes):
+            // the class once more with the scan front, synchronously, and from now on
+            C.front = C.front_used = FRONT_SCAN;
+            C.redone = true;
+            enqueue_class(b, C, false, false);
+            ck(hipStreamSynchronize(b->stream));
+        }
+        b->front_used |= C.front_used;
         for (int attempt = 0; attempt < 3; attempt++) {
             if (!C.h_misc[1] && C.h_misc[0] <= C.cap) break;
             C.cap = std::max<uint32_t>(C.h_misc[0] + 1024, C.cap * 2);  // candidate table overflow: grow, redo

@@ -20,7 +20,7 @@ namespace zflac {
 // ----------------------------------------------------------------------------------
 // k_scan: frame-sync candidates per 32 KiB chunk
 // ----------------------------------------------------------------------------------
-__device__ inline uint32_t ff_mask(uint32_t d) { return ((d & 0x7F7F7F7Fu) + 0x01010101u) & d & 0x80808080u; }
+// (ff_mask, sync_mask, sync_any: device_common.h, shared with k_hop)
 
 // Calls fn(position) for every candidate in the 16-byte window `v` at `ws` that lies in
 // [lo, hi). Windows are 16-byte aligned.
@@ -50,28 +50,6 @@ __device__ inline void scan_window(const uint8_t* in, uint64_t ws, uint64_t lo, 
 // A wave's 16-byte windows are consecutive per lane, so the 16 bytes after a lane's window
 // are the next lane's window (DPP wave_shl:1); lane 63, and a lane whose next window lies
 // past the chunk (zeroed), read them from memory.
-// Bit 7 of byte i set where byte i of d is 0xFF and the byte after it (byte i + 1, or the
-// first byte of dn for i = 3) is 0xF8 or 0xF9: a frame sync code (src/zflac.zig:351-352).
-// Exact per byte (no borrow between bytes).
-__device__ __forceinline__ uint32_t sync_mask(uint32_t d, uint32_t dn) {
-    const uint32_t nxt = __builtin_amdgcn_alignbyte(dn, d, 1);  // byte i = the byte after byte i of d
-    const uint32_t y = (nxt & 0xFEFEFEFEu) ^ 0xF8F8F8F8u;        // zero bytes: next is 0xF8 / 0xF9
-    const uint32_t zero = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
-    return ff_mask(d) & zero;
-}
-
-// Nonzero iff some byte i of d is 0xFF and the byte after it 0xF8 / 0xF9: the same test as
-// sync_mask, as an existence test only. Byte i of t is zero exactly at a sync code, and
-// (t - 0x01..01) & ~t & 0x80..80 is nonzero iff t has a zero byte (the borrows can mark a
-// byte above a zero one, never create a mark without one). ~5 VALU per dword against
-// sync_mask's ~10: k_scan runs it on every window and the exact masks only where it fires
-// (a sync code, or a 0xFF 0xF8|F9 pair in the coded bits: ~1 in 7 wave-windows of 1 KiB).
-__device__ __forceinline__ uint32_t sync_any(uint32_t d, uint32_t dn) {
-    const uint32_t nxt = __builtin_amdgcn_alignbyte(dn, d, 1);
-    const uint32_t t = ~d | ((nxt & 0xFEFEFEFEu) ^ 0xF8F8F8F8u);
-    return (t - 0x01010101u) & ~t & 0x80808080u;
-}
-
 // (Call at wave-uniform points: DPP reads the neighbour lane's registers.)
 __device__ __forceinline__ uint32_t lane_above(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true);  // wave_shl:1

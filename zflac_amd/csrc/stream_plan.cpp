@@ -93,4 +93,39 @@ void plan_stream(StreamPlan& s, const uint8_t* d, size_t n) {
     if (channels_count(s.first.chan_code) != s.nch) { s.host_err = E_INCONSISTENT_PARAMETERS; return; }  // :386
 }
 
+uint32_t hop_frames(const StreamPlan& s) {
+    const uint64_t bs = s.si.min_block;
+    return bs ? (uint32_t)((s.si.total + bs - 1) / bs) : 0;
+}
+
+bool hop_stream_ok(const StreamPlan& s, uint32_t max_frames) {
+    if (s.host_err || s.no_frames || s.si.total == 0) return false;
+    if (s.si.min_block != s.si.max_block || s.si.min_block < 16 || s.first.byte1 != 0xF8) return false;
+    if ((s.si.total + s.si.min_block - 1) / s.si.min_block > max_frames) return false;
+    return s.len - s.frames_begin < (1ull << 31);
+}
+
+Front plan_hop(const StreamPlan* const* streams, size_t n, FrontMode mode, const HopLimits& lim, HopDesc* out,
+               uint64_t* total_frames) {
+    if (total_frames) *total_frames = 0;
+    if (mode == FRONT_FORCE_SCAN || n == 0) return FRONT_SCAN;
+    if (mode == FRONT_AUTO && n < lim.min_streams) return FRONT_SCAN;
+    uint64_t f0 = 0;
+    for (size_t i = 0; i < n; i++) {
+        const StreamPlan& s = *streams[i];
+        if (!hop_stream_ok(s, lim.max_frames)) return FRONT_SCAN;
+        const uint32_t nf = hop_frames(s);
+        if (f0 + nf > 0x7FFFFFFFull) return FRONT_SCAN;
+        if (out) {
+            out[i].n_frames = nf;
+            out[i].f0 = (uint32_t)f0;
+            out[i].units = (uint32_t)s.si.min_block * (uint32_t)s.nch;
+            out[i].guess = (uint32_t)((s.len - s.frames_begin) / nf);
+        }
+        f0 += nf;
+    }
+    if (total_frames) *total_frames = f0;
+    return FRONT_HOP;
+}
+
 }  // namespace zflac

@@ -41,4 +41,26 @@ uint8_t justify_of(uint32_t bps);  // left-justify shift (src/zflac.zig:287-306)
 // Host planning of one stream: metadata and the first frame header.
 void plan_stream(StreamPlan& s, const uint8_t* d, size_t n);
 
+// ---- the choice of front (k_scan or k_hop, hop.hip) ----------------------------------
+enum Front : int { FRONT_SCAN = 1, FRONT_HOP = 2 };  // ZFLAC_FRONT_* of zflac_hip.h
+enum FrontMode : int { FRONT_AUTO = 0, FRONT_FORCE_SCAN = 1, FRONT_FORCE_HOP = 2 };
+
+struct HopLimits {
+    uint32_t max_frames = HOP_MAX_FRAMES;    // frames per stream, at most
+    uint32_t min_streams = HOP_MIN_STREAMS;  // streams per class, at least (not applied when forced)
+};
+
+// Can k_hop follow this stream? A STREAMINFO total, fixed blocking (first frame 0xF8 and
+// STREAMINFO min block == max block >= 16: frame i carries the coded number i and zflac reads
+// exactly ceil(total / block) frames), at most max_frames of them, and under 2 GiB of frames
+// (k_hop's positions are 32-bit).
+bool hop_stream_ok(const StreamPlan& s, uint32_t max_frames);
+// Frames of a hop-eligible stream: ceil(total / block).
+uint32_t hop_frames(const StreamPlan& s);
+// The front of a class of `n` streams, and for FRONT_HOP its per-stream descriptors (f0 the
+// running sum of n_frames, guess = frame bytes / n_frames) and their frame total.
+// FRONT_FORCE_HOP still needs every stream to pass hop_stream_ok; it only drops min_streams.
+Front plan_hop(const StreamPlan* const* streams, size_t n, FrontMode mode, const HopLimits& lim, HopDesc* out,
+               uint64_t* total_frames);
+
 }  // namespace zflac
