@@ -192,7 +192,13 @@ struct DecodeArgs {
                             // kernels). The normal launch never includes it: the host issues it
                             // after a run whose order-8 launch reported a bucket outside
                             // full_mask (bucket_used), so a correct prediction costs no launch
+    uint32_t wb_bytes;      // bytes of `out` (16-byte aligned, at most WB_RSRC_MAX) that the staged 16-bit
+                            // write-back may address through a buffer resource; 0: through the pointer
+                            // (larger outputs, the sequential path's sub-ranges, ZFLAC_STAGE_WB=ptr)
 };
+// A masked row of the resource write-back stores at an offset with bit 31 set, which must lie
+// past the resource for the buffer unit to drop it.
+constexpr uint64_t WB_RSRC_MAX = 0x80000000ull;
 
 // Grid (workgroups) of the `rest` launch: a few waves striding over the frame groups (the
 // groups of unpredicted buckets; a misprediction costs time, never correctness).

@@ -378,7 +378,8 @@ struct Stage {
     static constexpr uint32_t PIECES = MONO ? 4u : 8u;    // 16-byte pieces per frame and chunk
     static constexpr uint32_t ROW_FRAMES = 64u / PIECES;  // frames per write-back row
     using Mask = std::conditional_t<MONO, uint64_t, uint32_t>;
-    guint4* out;     // the output buffer (wave-uniform, held in VGPRs)
+    guint4* out;     // the output buffer (wave-uniform, held in VGPRs): the pointer write-back
+    __amdgpu_buffer_rsrc_t rs;  // the same buffer as a raw resource (SGPRs): the resource write-back
     uint32_t gq[4];  // quad index (from `out`) of this lane's piece of row t at sample 0
     Mask mask;       // frames (bit j) whose staged chunk is valid: fast, not redone, writable
     uint32_t base;   // first sample of the staged chunk
@@ -414,17 +415,34 @@ struct Stage {
             *dst = __builtin_bit_cast(u32x4v, v[t]);
         }
     }
+    // The same rows through the buffer resource (WB_RSRC launches: the class's output is at most
+    // WB_RSRC_MAX bytes). The offset is 32 bits, one v_add_lshl, and a masked row sets its bit 31,
+    // which lies past the resource: the buffer unit drops the store, no dummy line is written. The
+    // row's bit comes from a scalar shift of ~mask by the row's first frame, then one per-lane
+    // shift by the lane's frame within the row; v_lshl_or moves it to bit 31 and drops the rest.
+    __device__ __forceinline__ void store_rsrc(const uint4 (&v)[4]) const {
+        const uint32_t bq = MONO ? base / 8u : base / 4u;
+        const uint32_t fr = lane() / PIECES;  // this lane's frame within a row
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const uint32_t dead = (uint32_t)((Mask)~mask >> (t * (int)ROW_FRAMES)) >> fr;
+            const uint32_t off = ((gq[t] + bq) << 4) | (dead << 31);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v[t]), rs, (int)off, 0, 0);
+        }
+    }
+    template <bool WBR>
     __device__ __forceinline__ void flush(uint4* dummy) {
         uint4 v[4];
         read(v);
-        store(v, dummy);
+        if constexpr (WBR) store_rsrc(v);
+        else store(v, dummy);
     }
 };
 template <int LAY>
 using StageOf = Stage<LAY == LAY_MONO>;
 // 16-bit containers, stereo or mono: PCM goes through the stage
 template <int KIND, int LAY>
-__device__ __forceinline__ constexpr bool staged() { return KIND == 1 && LAY != LAY_MULTI; }
+__host__ __device__ __forceinline__ constexpr bool staged() { return KIND == 1 && LAY != LAY_MULTI; }
 
 template <int KIND>
 __device__ __forceinline__ constexpr bool pend_two() { return KIND == 2; }
@@ -444,10 +462,10 @@ __device__ __forceinline__ uint32_t dummy_slot() {
 // k_decode's junk slots are the first word slots of the wave's output stage: the flush has
 // just read every staged piece into registers (LDS operations of a wave complete in order),
 // and the chunk's own pieces are written only after this top-up.
-template <int KIND, int LAY, bool WALK>
+template <int KIND, int LAY, bool WALK, bool WBR>
 __device__ __forceinline__ void topup_st(Rdr& rd, Pend& pd, StageOf<LAY>& sg, uint4* dummy) {
     if constexpr (!WALK) {
-        if constexpr (staged<KIND, LAY>()) sg.flush(dummy);
+        if constexpr (staged<KIND, LAY>()) sg.template flush<WBR>(dummy);
         else pd.flush(pend_two<KIND>());
     }
     rd.template topup<topup_quads<KIND>()>();
@@ -1445,9 +1463,11 @@ __device__ __forceinline__ void fast_chunk(LaneCtx& L, Rdr& rd, Pred<KIND, M>& p
 }
 
 // Decode (WALK = false) or walk (WALK = true) one subframe per lane, chunk by chunk.
-template <int KIND, int M, int LAY, bool WALK, bool MIX = false>
+// WBR: the staged write-back goes through a buffer resource over `out_bytes` of `out`.
+template <int KIND, int M, int LAY, bool WALK, bool MIX = false, bool WBR = false>
 __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx& fc, void* out, int nch, int c,
-                                    int32_t c1m, uint32_t bs_max, void* dummy_base) {
+                                    int32_t c1m, uint32_t bs_max, void* dummy_base, uint32_t out_bytes = 0) {
+    static_assert(!WBR || (!WALK && staged<KIND, LAY>()), "only the staged write-back has a resource form");
     constexpr int L_ = WALK ? CHUNK : DEC_CHUNK;
     static_assert(L_ % hist_len<M>() == 0 && L_ % 16 == 0, "a chunk holds whole history rings and output groups");
     uint4* const dummy = reinterpret_cast<uint4*>(dummy_base) + dummy_slot();
@@ -1461,9 +1481,21 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
     // (in VGPRs: as a wave-uniform kernel argument it stayed part of the 16-SGPR tuple of the
     // argument load, which the allocator spilled to VGPR lanes and restored with 16 v_readlane
     // at every chunk start's write-back)
-    uint64_t outv = reinterpret_cast<uintptr_t>(out);
-    asm volatile("" : "+v"(outv));
-    sg.out = reinterpret_cast<guint4*>(outv);
+    // (the resource form holds four SGPRs instead: made from values read with v_readfirstlane
+    // once per subframe, which the allocator cannot fetch again from the argument tuple)
+    if constexpr (WBR) {
+        const uint64_t o = reinterpret_cast<uintptr_t>(out);
+        // (each half widened as unsigned: the builtin returns int, and a sign-extended low half
+        // would set every high bit of a pointer whose bit 31 is set)
+        const uint64_t ou = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(o >> 32)) << 32) |
+                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)o);
+        sg.rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(ou), (short)0,
+                                                  (int)__builtin_amdgcn_readfirstlane(out_bytes), BUFFER_RSRC_WORD3);
+    } else {
+        uint64_t outv = reinterpret_cast<uintptr_t>(out);
+        asm volatile("" : "+v"(outv));
+        sg.out = reinterpret_cast<guint4*>(outv);
+    }
     if constexpr (!WALK && staged<KIND, LAY>()) {
 #pragma unroll
         for (int t = 0; t < 4; t++)  // frame row_frame(t)'s output, in quads (fc.packed: < 2^32)
@@ -1501,7 +1533,7 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
 #ifdef ZFLAC_PROBE
         const uint64_t p0 = __builtin_amdgcn_s_memtime();
 #endif
-        topup_st<KIND, LAY, WALK>(rd, pd, sg, dummy);
+        topup_st<KIND, LAY, WALK, WBR>(rd, pd, sg, dummy);
         sg.mask = 0;  // flushed
 #ifdef ZFLAC_PROBE
         const uint64_t p1 = __builtin_amdgcn_s_memtime();
@@ -1690,7 +1722,7 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
 #endif
     if constexpr (!WALK) {
         if constexpr (staged<KIND, LAY>()) {
-            sg.flush(dummy);
+            sg.template flush<WBR>(dummy);
         } else {
             pd.flush(pend_two<KIND>());
         }
@@ -1854,7 +1886,9 @@ __host__ __device__ constexpr int dec_min_waves() {
     if (KIND == 2 && LAY == LAY_STEREO && MB > 4) return 1;
     return 2;
 }
-template <int KIND, int LAY, int MB, bool MIX>
+// WBR (16-bit stereo / mono only): the staged PCM goes back through a buffer resource
+// (Stage::store_rsrc); chosen per launch by the host (DecodeArgs::wb_bytes).
+template <int KIND, int LAY, int MB, bool MIX, bool WBR = false>
 __global__ __launch_bounds__(DEC_THREADS, (dec_min_waves<KIND, LAY, MB, MIX>())) void k_decode(DecodeArgs a) {
 #ifdef ZFLAC_DEC_PRIO
     // (experiment) decode waves ahead of the md5 hub's waves on a shared SIMD
@@ -1926,7 +1960,7 @@ __global__ __launch_bounds__(DEC_THREADS, (dec_min_waves<KIND, LAY, MB, MIX>()))
             }
         }
         if (!rest && mb != (uint32_t)MB + (MIX ? MIX_BIT : 0u)) continue;  // another launch decodes this wave's frames
-        run_subframe<KIND, MB, LAY, false, MIX>(L, rd, fc, a.out, nch, c, c1m, bs_act, a.dummy);
+        run_subframe<KIND, MB, LAY, false, MIX, WBR>(L, rd, fc, a.out, nch, c, c1m, bs_act, a.dummy, a.wb_bytes);
 
         // ---- frame end and record -----------------------------------------------------
         uint32_t endbits = (rd.pos() + 7) & ~7u;  // alignToByte (:546)
@@ -2002,47 +2036,45 @@ __host__ __forceinline__ bool bucket_launched(const DecodeArgs& a, uint32_t mb, 
 // the `rest` launch (launch_decode_mix with rest_only), which the host issues only after a
 // run that needed it (each empty launch costs ~5 us of a ~0.55 ms step, and far more with
 // several runs in flight, where it waits for LDS to dispatch).
-// Dynamic LDS above 64 KiB (the 32-bit-container units' larger rings) must be allowed per kernel.
-template <int KIND, int LAY, int MB, bool MIX>
-__host__ hipError_t allow_dec_lds() {
-    if constexpr (DEC_LDS_BYTES <= 64 * 1024) {
-        return hipSuccess;
-    } else {
+// The staged write-back of a launch: through the buffer resource when the host offers one
+// (DecodeArgs::wb_bytes != 0) and the kernel stages its PCM, else through the pointer.
+template <int KIND, int LAY>
+__host__ __forceinline__ bool wb_rsrc(const DecodeArgs& a) {
+    return staged<KIND, LAY>() && a.wb_bytes != 0;
+}
+
+// One bucket kernel, either write-back form. Dynamic LDS above 64 KiB (four waves' rings and
+// stages; the 32-bit-container units' larger rings) must be allowed per kernel.
+template <int KIND, int LAY, int MB, bool MIX, bool WBR>
+__host__ hipError_t launch_bucket_wb(const DecodeArgs& a, dim3 g, hipStream_t st) {
+    if constexpr (DEC_LDS_BYTES > 64 * 1024) {
         static std::atomic<uint64_t> lds_set{0};
-        return set_lds_limit(lds_set, reinterpret_cast<const void*>(&k_decode<KIND, LAY, MB, MIX>), DEC_LDS_BYTES);
+        if (const hipError_t e = set_lds_limit(lds_set, reinterpret_cast<const void*>(&k_decode<KIND, LAY, MB, MIX, WBR>),
+                                               DEC_LDS_BYTES);
+            e != hipSuccess)
+            return e;
     }
+    hipLaunchKernelGGL((k_decode<KIND, LAY, MB, MIX, WBR>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
+    return hipSuccess;
 }
-template <int KIND, int LAY>
-__host__ hipError_t allow_dec_lds_all() {
-    hipError_t e = allow_dec_lds<KIND, LAY, 4, false>();
-    if (e == hipSuccess) e = allow_dec_lds<KIND, LAY, 8, false>();
-    if (e == hipSuccess) e = allow_dec_lds<KIND, LAY, 12, false>();
-    if (e == hipSuccess) e = allow_dec_lds<KIND, LAY, 16, false>();
-    if (e == hipSuccess) e = allow_dec_lds<KIND, LAY, 32, false>();
-    return e;
-}
-template <int KIND, int LAY>
-__host__ hipError_t allow_dec_lds_mix() {
-    hipError_t e = allow_dec_lds<KIND, LAY, 8, true>();
-    if (e == hipSuccess) e = allow_dec_lds<KIND, LAY, 32, true>();
-    return e;
+template <int KIND, int LAY, int MB, bool MIX>
+__host__ hipError_t launch_bucket(const DecodeArgs& a, dim3 g, hipStream_t st) {
+    if constexpr (staged<KIND, LAY>()) {
+        if (wb_rsrc<KIND, LAY>(a)) return launch_bucket_wb<KIND, LAY, MB, MIX, true>(a, g, st);
+    }
+    return launch_bucket_wb<KIND, LAY, MB, MIX, false>(a, g, st);
 }
 
 template <int KIND, int LAY>
 hipError_t launch_decode_layout(const DecodeArgs& a, uint32_t max_frames, hipStream_t st) {
     if (a.rest_only) return hipSuccess;
-    if (const hipError_t e = allow_dec_lds_all<KIND, LAY>(); e != hipSuccess) return e;
     const dim3 g = decode_grid<KIND, LAY>(a, max_frames);
-    hipLaunchKernelGGL((k_decode<KIND, LAY, 8, false>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    if (bucket_launched(a, 4, false))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 4, false>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    if (bucket_launched(a, 12, false))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 12, false>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    if (bucket_launched(a, 16, false))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 16, false>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    if (bucket_launched(a, 32, false))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 32, false>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    return hipGetLastError();
+    hipError_t e = launch_bucket<KIND, LAY, 8, false>(a, g, st);
+    if (e == hipSuccess && bucket_launched(a, 4, false)) e = launch_bucket<KIND, LAY, 4, false>(a, g, st);
+    if (e == hipSuccess && bucket_launched(a, 12, false)) e = launch_bucket<KIND, LAY, 12, false>(a, g, st);
+    if (e == hipSuccess && bucket_launched(a, 16, false)) e = launch_bucket<KIND, LAY, 16, false>(a, g, st);
+    if (e == hipSuccess && bucket_launched(a, 32, false)) e = launch_bucket<KIND, LAY, 32, false>(a, g, st);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // Waves with CONSTANT / VERBATIM lanes (bucket 8 or 32 + MIX_BIT), after the pure kernels.
@@ -2050,20 +2082,18 @@ hipError_t launch_decode_layout(const DecodeArgs& a, uint32_t max_frames, hipStr
 // verbatim lanes) on a small grid, for the groups of buckets without a launch of their own.
 template <int KIND, int LAY>
 hipError_t launch_decode_mix(const DecodeArgs& a, uint32_t max_frames, hipStream_t st) {
-    if (const hipError_t e = allow_dec_lds_mix<KIND, LAY>(); e != hipSuccess) return e;
     const dim3 g = decode_grid<KIND, LAY>(a, max_frames);
     if (a.rest_only) {
         DecodeArgs r = a;
         r.rest = 1;
         const dim3 gr(g.x < SPARSE_DECODE_BLOCKS ? g.x : SPARSE_DECODE_BLOCKS);
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 32, true>), gr, dim3(DEC_THREADS), DEC_LDS_BYTES, st, r);
-        return hipGetLastError();
+        const hipError_t e = launch_bucket<KIND, LAY, 32, true>(r, gr, st);
+        return e != hipSuccess ? e : hipGetLastError();
     }
-    if (bucket_launched(a, 8, true))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 8, true>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    if (bucket_launched(a, 32, true))
-        hipLaunchKernelGGL((k_decode<KIND, LAY, 32, true>), g, dim3(DEC_THREADS), DEC_LDS_BYTES, st, a);
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    if (bucket_launched(a, 8, true)) e = launch_bucket<KIND, LAY, 8, true>(a, g, st);
+    if (e == hipSuccess && bucket_launched(a, 32, true)) e = launch_bucket<KIND, LAY, 32, true>(a, g, st);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // namespace zflac

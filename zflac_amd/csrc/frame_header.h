@@ -95,6 +95,61 @@ constexpr bool crc8_fold_matches_table() {
 }
 static_assert(crc8_fold_matches_table(), "register CRC-8 = table CRC-8");
 
+// Does a header of n bytes (6..16, its CRC-8 byte last) carry the right CRC-8? h0..h3 hold
+// header bytes 0..15 in memory order (byte 0 in the low bits of h0), whatever follows the
+// header in the bytes from n on. With init 0 and no final xor, the CRC-8 of a message followed
+// by its own CRC-8 is 0, and zero bytes after that leave it 0 (x is invertible modulo the
+// polynomial), while a wrong CRC-8 leaves a nonzero remainder that zeros never clear. So the
+// bytes from n on are zeroed and the 16 go through 3-byte steps at constant byte positions (two,
+// then one more per three bytes the header reaches), where a loop over the header's own length
+// picks every byte with a computed index and ends with one or two single-byte steps (k_hop).
+constexpr uint32_t crc8_keep_bytes(uint32_t be_word, int bytes) {  // the first `bytes` (<= 0: none, >= 4: all)
+    const int s = bytes < 0 ? 0 : (bytes > 4 ? 32 : 8 * bytes);
+    return be_word & (uint32_t)(0xFFFFFFFF00000000ull >> s);
+}
+constexpr bool crc8_header_ok(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3, uint32_t n) {
+    const uint32_t w0 = __builtin_bswap32(h0);  // n >= 6: whole
+    const uint32_t w1 = crc8_keep_bytes(__builtin_bswap32(h1), (int)n - 4);
+    // (crc8_3 shifts its 24-bit group up by 8: whatever a group carries above bit 23 falls out)
+    uint32_t crc = crc8_3(0, w0 >> 8);
+    crc = crc8_3(crc, (w0 << 16) | (w1 >> 16));
+    // the groups from byte 6 on only where the header reaches them (all zero otherwise): most
+    // headers are 6 or 7 bytes long
+    if (n > 6) {
+        const uint32_t w2 = crc8_keep_bytes(__builtin_bswap32(h2), (int)n - 8);
+        crc = crc8_3(crc, (w1 << 8) | (w2 >> 24));
+        if (n > 9) {
+            const uint32_t w3 = crc8_keep_bytes(__builtin_bswap32(h3), (int)n - 12);
+            crc = crc8_3(crc, w2);
+            if (n > 12) crc = crc8_1(crc8_3(crc, w3 >> 8), w3 & 0xFFu);
+        }
+    }
+    return crc == 0;
+}
+constexpr bool crc8_header_ok_matches_table() {
+    const Crc8Table t = make_crc8_table();
+    uint32_t x = 2463534242u;
+    for (int k = 0; k < 64; k++) {
+        for (uint32_t n = 6; n <= 16; n++) {
+            uint8_t b[16] = {};
+            for (int i = 0; i < 16; i++) {
+                x = x * 1103515245u + 12345u;
+                b[i] = (uint8_t)(x >> 16);
+            }
+            uint32_t crc = 0;
+            for (uint32_t i = 0; i + 1 < n; i++) crc = t.t[crc ^ b[i]];
+            for (int bad = 0; bad < 2; bad++) {  // the right CRC-8 byte, then a wrong one
+                b[n - 1] = (uint8_t)(crc ^ (bad ? 1u + (x >> 24) % 255u : 0u));
+                uint32_t h[4] = {};
+                for (int i = 0; i < 16; i++) h[i / 4] |= (uint32_t)b[i] << (8 * (i % 4));
+                if (crc8_header_ok(h[0], h[1], h[2], h[3], n) != (bad == 0)) return false;
+            }
+        }
+    }
+    return true;
+}
+static_assert(crc8_header_ok_matches_table(), "fixed-length header CRC-8 = table CRC-8, lengths 6..16");
+
 // ----------------------------------------------------------------------------------
 // Frame header, exact zflac semantics (src/zflac.zig:343-375, 203-214, 407).
 // `err` holds errors raised before the first-frame / consistency checks; a missing

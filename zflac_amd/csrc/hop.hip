@@ -26,9 +26,18 @@ constexpr int HOP_WINDOW = HOP_LANES * HOP_LANE_BYTES;  // 1 KiB
 constexpr int HOP_PROBES = 16;       // windows per hop, at most
 constexpr int HOP_THREADS = 64;      // one wave: four streams
 
+// Minimum over the 16 lanes of a stream's group. A group is one DPP row, so the four steps are
+// v_min_u32 with a DPP operand (the lane's quad neighbours, then the row rotated by 4 and by 8)
+// and no LDS permute. Lanes of a group are active together wherever this is called.
 __device__ __forceinline__ uint32_t hop_group_min(uint32_t v) {
-#pragma unroll
-    for (int m = HOP_LANES / 2; m; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m, HOP_LANES));
+    static_assert(HOP_LANES == 16, "a group is one DPP row");
+    auto step = [](uint32_t x, auto ctrl) {
+        return min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, decltype(ctrl)::value, 0xF, 0xF, false));
+    };
+    v = step(v, std::integral_constant<int, 0xB1>{});   // quad_perm:[1,0,3,2]
+    v = step(v, std::integral_constant<int, 0x4E>{});   // quad_perm:[2,3,0,1]
+    v = step(v, std::integral_constant<int, 0x124>{});  // row_ror:4
+    v = step(v, std::integral_constant<int, 0x128>{});  // row_ror:8
     return v;
 }
 
@@ -50,42 +59,56 @@ __device__ __forceinline__ HopHit hop_probe_lane(const __amdgpu_buffer_rsrc_t rs
     if (off < 0 || off >= (int64_t)end) return hit;
     // 80 bytes: the lane's 64 and the 16 after them, so that a header (at most 16 bytes) that
     // starts in its last byte is whole; past the stream the buffer unit answers with zeros
-    uint32_t d[20];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)off, j * 16, 0));
-        d[4 * j] = v.x;
-        d[4 * j + 1] = v.y;
-        d[4 * j + 2] = v.z;
-        d[4 * j + 3] = v.w;
+    // (Twenty named registers, not an array: an array indexed inside an unrolled loop or a lambda is
+    // still memory when the optimiser first meets a select between two of its elements, which it
+    // folds into one load at a selected address, and that ends as scratch stores on every probe.)
+#define HOP_LOAD(j, a, b, c, e)                                                                                    \
+    uint32_t a, b, c, e;                                                                                           \
+    {                                                                                                              \
+        const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)off, (j) * 16, 0)); \
+        a = v.x, b = v.y, c = v.z, e = v.w;                                                                        \
     }
-    uint32_t any = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) any |= sync_any(d[i], d[i + 1]);
-    if (!any) return hit;
-    uint64_t cand = 0;  // bit b: a sync code at byte b of the lane's 64
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        cand |= (uint64_t)((sync_mask(d[i], d[i + 1]) * 0x00204081u) >> 28 & 15u) << (4 * i);
-    while (cand) {
-        const uint32_t b = (uint32_t)__ffsll((unsigned long long)cand) - 1u;
-        cand &= cand - 1;
-        const uint64_t rel = (uint64_t)off + b;
+    HOP_LOAD(0, d0, d1, d2, d3)
+    HOP_LOAD(1, d4, d5, d6, d7)
+    HOP_LOAD(2, d8, d9, d10, d11)
+    HOP_LOAD(3, d12, d13, d14, d15)
+    HOP_LOAD(4, d16, d17, d18, d19)
+#undef HOP_LOAD
+    // The sync codes of the lane's 64 bytes, found once (the cheaper existence test that k_scan
+    // runs first is no saving here: the wanted header makes it fire in every probe of every
+    // group). Two registers of 8 dwords each: bit 8 y + x of c0 is byte y of dword x, of c1 byte y
+    // of dword 8 + x, so a dword's four marks (bits 7, 15, 23, 31) go in with one shift and one or.
+    const uint32_t c0_all = sync_mask(d0, d1) >> 7 | sync_mask(d1, d2) >> 6 | sync_mask(d2, d3) >> 5 |
+                            sync_mask(d3, d4) >> 4 | sync_mask(d4, d5) >> 3 | sync_mask(d5, d6) >> 2 |
+                            sync_mask(d6, d7) >> 1 | sync_mask(d7, d8);
+    const uint32_t c1_all = sync_mask(d8, d9) >> 7 | sync_mask(d9, d10) >> 6 | sync_mask(d10, d11) >> 5 |
+                            sync_mask(d11, d12) >> 4 | sync_mask(d12, d13) >> 3 | sync_mask(d13, d14) >> 2 |
+                            sync_mask(d14, d15) >> 1 | sync_mask(d15, d16);
+    uint32_t c0 = c0_all, c1 = c1_all;
+    while (c0 | c1) {  // (in no order of position: the lowest hit is kept by a minimum below)
+        const bool first = c0 != 0;
+        const uint32_t cc = first ? c0 : c1;
+        const uint32_t bit = (uint32_t)__ffs((int)cc) - 1u;
+        c0 = first ? cc & (cc - 1u) : c0;
+        c1 = first ? c1 : cc & (cc - 1u);
+        const uint32_t dw = (bit & 7u) + (first ? 0u : 8u), sb = bit >> 3;
+        const uint64_t rel = (uint64_t)off + 4u * dw + sb;
         if (rel < lo || rel >= end) continue;
-        // dwords b/4 .. b/4 + 4 picked with constant indices (80 v_cndmask per candidate; an
-        // indexed register array, or a select tree the compiler folds into one, becomes scratch
-        // stores on every probe), then v_alignbyte by b & 3: header bytes 0..15 in four registers
-        const uint32_t dw = b >> 2, sb = b & 3u;
-        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0, w4 = 0;
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const bool here = dw == (uint32_t)i;
-            w0 = here ? d[i] : w0;
-            w1 = here ? d[i + 1] : w1;
-            w2 = here ? d[i + 2] : w2;
-            w3 = here ? d[i + 3] : w3;
-            w4 = here ? d[i + 4] : w4;
-        }
+        // dwords dw .. dw + 4 in two levels of selects: the eight dwords from quad dw / 4 on (3
+        // v_cndmask each), then five of those from dword dw % 4 on (3 each): 39 v_cndmask, where one
+        // level over the 16 positions took 80. Then v_alignbyte by sb: header bytes 0..15 in four
+        // registers
+        const bool q1 = (dw >> 2) == 1u, q2 = (dw >> 2) == 2u, q3 = (dw >> 2) == 3u;
+#define HOP_QUAD(a, b, c, e) (q3 ? (e) : (q2 ? (c) : (q1 ? (b) : (a))))
+        const uint32_t e0 = HOP_QUAD(d0, d4, d8, d12), e1 = HOP_QUAD(d1, d5, d9, d13), e2 = HOP_QUAD(d2, d6, d10, d14),
+                       e3 = HOP_QUAD(d3, d7, d11, d15), e4 = HOP_QUAD(d4, d8, d12, d16), e5 = HOP_QUAD(d5, d9, d13, d17),
+                       e6 = HOP_QUAD(d6, d10, d14, d18), e7 = HOP_QUAD(d7, d11, d15, d19);
+#undef HOP_QUAD
+        const bool r1 = (dw & 3u) == 1u, r2 = (dw & 3u) == 2u, r3 = (dw & 3u) == 3u;
+#define HOP_WORD(a, b, c, e) (r3 ? (e) : (r2 ? (c) : (r1 ? (b) : (a))))
+        const uint32_t w0 = HOP_WORD(e0, e1, e2, e3), w1 = HOP_WORD(e1, e2, e3, e4), w2 = HOP_WORD(e2, e3, e4, e5),
+                       w3 = HOP_WORD(e3, e4, e5, e6), w4 = HOP_WORD(e4, e5, e6, e7);
+#undef HOP_WORD
         const uint32_t h0 = __builtin_amdgcn_alignbyte(w1, w0, sb), h1 = __builtin_amdgcn_alignbyte(w2, w1, sb),
                        h2 = __builtin_amdgcn_alignbyte(w3, w2, sb), h3 = __builtin_amdgcn_alignbyte(w4, w3, sb);
         auto at = [h0, h1, h2, h3](uint32_t i) -> uint32_t {  // byte i: v_perm from 8 bytes, zeros above
@@ -93,13 +116,15 @@ __device__ __forceinline__ HopHit hop_probe_lane(const __amdgpu_buffer_rsrc_t rs
             return (i & 8u) ? __builtin_amdgcn_perm(h3, h2, sel) : __builtin_amdgcn_perm(h1, h0, sel);
         };
         const uint64_t avail = S.in_end - (abase + rel);
-        const FrameHdr h = parse_frame_header_t<2>(at, avail, S.si_rate, nullptr);
+        // the fields, then the CRC-8 over the header's own length in a fixed number of steps
+        // (crc8_header_ok; read only where the header is whole: hdr_len is 6..16 there)
+        FrameHdr h = parse_frame_header_t<0>(at, avail, S.si_rate, nullptr);
+        h.crc_ok = h.err == 0 && !h.crc_eof && crc8_header_ok(h0, h1, h2, h3, h.hdr_len);
         if (!candidate_ok(h, S)) continue;
         uint64_t num;
         if (!coded_number_value(at, avail, num)) continue;
         if (num == want) {
-            // (ascending: the first is the lowest)
-            if (hit.pos == ~0u && (uint64_t)h.bs * S.nch == want_units) hit.pos = (uint32_t)rel;
+            if ((uint64_t)h.bs * S.nch == want_units) hit.pos = min(hit.pos, (uint32_t)rel);  // the lowest
         } else if (num > want) {
             hit.higher = 1;
         }

@@ -437,6 +437,13 @@ DecodeArgs decode_args(Class& C) {
     a.dummy = C.dummy.p;
     a.sub_start = C.sub.p;
     a.group_mb = C.group_mb.p;
+    // the staged write-back's form, per launch: the buffer resource wherever it can cover the
+    // class's whole output (ZFLAC_STAGE_WB=ptr keeps the pointer form: tests, timing experiments)
+    const char* e = std::getenv("ZFLAC_STAGE_WB");
+    const bool wb_ptr = e && e[0] == 'p';
+    a.wb_bytes = !wb_ptr && C.out.n <= WB_RSRC_MAX && (reinterpret_cast<uintptr_t>(C.out.p) & 15) == 0
+                     ? (uint32_t)C.out.n
+                     : 0u;
     return a;
 }
 
