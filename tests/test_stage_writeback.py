@@ -1,4 +1,4 @@
-"""The staged PCM write-back of the 16-bit decode kernels (Stage::store / store_rsrc, decode.inc):
+"""The staged PCM write-back of the 16-bit decode kernels (Stage::store / store_rsrc, decode/pcm_stage.h):
 a chunk's 32 samples per frame go back to memory as whole rows at the next chunk start, through a
 buffer resource over the class's output (the default) or through the pointer (ZFLAC_STAGE_WB=ptr).
 A row of a frame that must not be written (an error frame, a redone chunk, a frame on the generic

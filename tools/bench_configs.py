@@ -41,6 +41,11 @@ ROWS = {
     "verbatim stereo 16-bit": (dict(channels=2, bps=16, predictor=0, stereo_mode=1, block_size=B), 256, SAT, False),
     "constant-heavy stereo 16-bit": (dict(channels=2, bps=16, stereo_mode=1, silence_every=1, block_size=B), 256, SAT,
                                      False),
+    # channel 0 constant in every frame: every wave runs the 32-bit stereo MIX kernels (bucket 8 / 32)
+    "constant-heavy stereo 24-bit LPC-8": (dict(channels=2, bps=24, stereo_mode=1, silence_every=1, order=8, precision=14,
+                                                block_size=B, noise_lsb=16.0), 256, SAT, False),
+    "constant-heavy stereo 24-bit LPC-32": (dict(channels=2, bps=24, stereo_mode=1, silence_every=1, order=32,
+                                                 precision=14, block_size=B, noise_lsb=16.0), 256, SAT, False),
     "mono 8-bit LPC-4": (dict(channels=1, bps=8, order=4, precision=7, block_size=B, noise_lsb=1.0, tone_amp=0.3), 256,
                          SAT, False),
     "stereo 12-bit M/S LPC-8": (dict(channels=2, bps=12, stereo_mode=10, order=8, block_size=B, noise_lsb=4.0), 256,

@@ -16,7 +16,11 @@ SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "hop.hip", "md5.hip", "c
                                             "resample.hip", "stream_plan.cpp", "resample_plan.cpp", "pipeline.cpp",
                                             "seq_planner.cpp", "md5_host.cpp", "abi.cpp")]
 HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "device_common.h", "launch.h", "stream_plan.h",
-                                           "resample_plan.h", "export_tile.h", "batch.h", "md5.hpp", "decode.inc")]
+                                           "resample_plan.h", "export_tile.h", "batch.h", "md5.hpp")]
+# the decode kernels' headers (decode.inc includes csrc/decode/*.h): dependencies of the decode_k* units only
+DECODE_HEADERS = [os.path.join(CSRC, "decode.inc")] + sorted(
+    os.path.join(CSRC, "decode", n) for n in os.listdir(os.path.join(CSRC, "decode")) if n.endswith(".h"))
+HEADERS += DECODE_HEADERS
 DEPS = SOURCES + HEADERS + [os.path.join(ROOT, "include", "zflac_hip.h")]
 ARCH = os.environ.get("ZFLAC_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -63,11 +67,11 @@ def lib_build_id(path: str | None = None) -> str | None:
 
 
 def _obj_deps(src: str):
-    """A unit's own source plus all headers (decode.inc only for the decode units). abi.cpp
+    """A unit's own source plus all headers (DECODE_HEADERS only for the decode units). abi.cpp
     embeds the fingerprint of every source, so it depends on all of them."""
     if src.endswith("abi.cpp"):
         return list(DEPS)
-    hdrs = [h for h in HEADERS if not h.endswith("decode.inc") or "decode_k" in src]
+    hdrs = [h for h in HEADERS if h not in DECODE_HEADERS or "decode_k" in src]
     return [src] + hdrs + [os.path.join(ROOT, "include", "zflac_hip.h")]
 
 

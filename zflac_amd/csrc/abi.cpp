@@ -541,8 +541,8 @@ int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
 }
 
 #ifdef ZFLAC_PROBE
-// Timing-probe build only (tools/probe.sh): cycle counters the decode kernels accumulate
-// behind the dummy store region of the first class; zeroed after reading.
+// Timing-probe build only (tools/probe.py, run through tools/gpu.sh probe): cycle counters the
+// decode kernels accumulate behind the dummy store region of the first class; zeroed after reading.
 extern "C" int zflac_hip_probe(zflac_batch* b, unsigned long long* out, int n) {
     if (!b || b->classes.empty() || n > (int)(PROBE_BYTES / 8)) return E_INVALID_ARGUMENT;
     auto& C = *b->classes[0];

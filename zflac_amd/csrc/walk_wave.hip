@@ -2,7 +2,7 @@
 //
 // Subframe c+1 starts where subframe c ends (src/zflac.zig:425-541 read order), so before
 // subframe c >= 1 can be decoded the bit length of subframes 0..c-1 must be known. k_walk
-// (decode.inc) gives each lane one frame: 64 independent serial chains per wave, the right
+// (decode/kernels.h) gives each lane one frame: 64 independent serial chains per wave, the right
 // shape when a launch has tens of thousands of frames. This kernel is the other shape: a
 // whole wave walks one frame, so a launch with few frames (one stream of a few thousand
 // frames, the sequential planner's probes) or with several subframes to walk per frame
@@ -28,22 +28,6 @@ namespace zflac {
 namespace {
 
 constexpr int WW_THREADS = 256;  // 4 waves (frames) per workgroup
-constexpr int WBUFFER_RSRC_WORD3 = 0x00020000;  // raw buffer, 32-bit data format (as decode.inc)
-
-template <int KIND>
-struct WKind;
-template <>
-struct WKind<0> {
-    static constexpr int W = 16;  // InterType bits (Rice k and escape width limits)
-};
-template <>
-struct WKind<1> {
-    static constexpr int W = 32;
-};
-template <>
-struct WKind<2> {
-    static constexpr int W = 64;
-};
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -229,12 +213,12 @@ __device__ bool unary_w(WaveWin& W, uint32_t& P, uint32_t end, uint32_t& q) {
 }
 
 // One subframe, same reads as walk_subframe + the residual loop of run_subframe<WALK> in
-// decode.inc (src/zflac.zig:426-541, 614-666); P moves to its end. False on any error: the
+// decode/subframe.h (src/zflac.zig:426-541, 614-666); P moves to its end. False on any error: the
 // frame's decode reports it (channel 0 fails at the same read), so the recorded starts of
 // later subframes do not matter then.
 template <int KIND>
 __device__ bool walk_subframe_w(WaveWin& W, uint32_t& P, uint32_t bs, int bps, int ubps, uint32_t end) {
-    constexpr int IW = WKind<KIND>::W;
+    constexpr int IW = Kind<KIND>::W;
     const uint32_t h8 = W.bits(P, 8);
     if (h8 >> 7) return false;  // :431
     const uint32_t type = (h8 >> 1) & 63u;
@@ -312,7 +296,7 @@ __global__ __launch_bounds__(WW_THREADS) void k_walk_wave(DecodeArgs a) {
         const uint64_t wlen = a.in_size > abase ? a.in_size - abase : 0;
         const uint32_t rbytes = (uint32_t)(wlen > 0x7FFFFFF0ull ? 0x7FFFFFF0ull : wlen);
         W.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.in) + abase, (short)0, (int)rbytes,
-                                                 WBUFFER_RSRC_WORD3);
+                                                 BUFFER_RSRC_WORD3);
         W.nwords = rbytes / 4u;
         W.init(0);
         // the frame header from the window (its at most 16 + 16 bytes are words 0..7)
@@ -320,7 +304,7 @@ __global__ __launch_bounds__(WW_THREADS) void k_walk_wave(DecodeArgs a) {
         const FrameHdr h = parse_frame_header_t<0>([&](uint32_t i) -> uint32_t { return W.byte(hb + i); },
                                                        S.in_end > pos ? S.in_end - pos : 0, S.si_rate, nullptr);
         const int bps = depth_bits(h.dcode, S.si_bps);
-        // the frame decodes only with these (setup_frame in decode.inc)
+        // the frame decodes only with these (setup_frame in decode/kernels.h)
         bool ok = !h.err && !h.crc_eof && channels_count(h.chan_code) == nch && bps >= 0;
         const uint64_t end_bytes = S.in_end > abase ? S.in_end - abase : 0;
         const uint32_t end = end_bytes * 8 > 0xFFFF0000ull ? 0xFFFF0000u : (uint32_t)(end_bytes * 8);
