@@ -1,7 +1,9 @@
 """Timing-probe run (experimental build with -DZFLAC_PROBE, tools/_build/lib_probe.so):
 cycles per chunk phase of k_walk and k_decode, summed over waves, for the C5 shard or one
 tiled stream of a BASELINE config (c2 / c3 / c4, 65,536 frames).
-Usage: ZFLAC_HIP_LIB=tools/_build/lib_probe.so python tools/probe.py [streams | c2 | c3 | c4]"""
+Usage: ZFLAC_HIP_LIB=tools/_build/lib_probe.so python tools/probe.py [streams | c2 | c3 | c4 | row:NAME |
+edges:CASE[:lane]], CASE a crafted stream of tests/rice_edges.py: the counters beside what tests/craft.py's
+model of the chunk loop predicts for them."""
 import ctypes
 import json
 import os
@@ -26,13 +28,23 @@ elif arg.startswith("row:"):  # a row of tools/bench_configs.py (substring of it
     st = synth.generate(**dict(cfg, n_samples=4096 * seg, seed=cfg.get("seed", 7)))
     streams = [synth.tile_flac(st, max(1, frames // seg))]
     n = name
+elif arg.startswith("edges:"):  # a crafted Rice-edge case (tests/rice_edges.py), with the model's prediction
+    from tests import craft, rice_edges  # noqa: E402
+
+    name, _, walk = arg[6:].partition(":")  # edges:CASE[:lane]: under the lane walk (k_walk's counters)
+    case = next(c for c in rice_edges.all_cases() if c.name == name)
+    streams = [case.cr.flac]
+    n = arg
+    model = {"decode": craft.predict_probe(case.cr)}
+    if walk == "lane" and case.cr.channels == 2:
+        model["walk"] = craft.predict_probe(case.cr, walk=True)
 else:
     cfg = {"c2": synth.config_c2, "c3": synth.config_c3, "c4": synth.config_c4}[arg]()
     seg = 512
     st = synth.generate(**dict(cfg, n_samples=4096 * seg, seed=cfg.get("seed", 7)))
     streams = [synth.tile_flac(st, 65536 // seg)]
     n = arg
-b = zflac_amd.Batch(streams, timing=True)
+b = zflac_amd.Batch(streams, timing=True, walk="lane" if arg.endswith(":lane") else None)
 L = _lib.load()
 fn = L.zflac_hip_probe
 fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
@@ -44,6 +56,8 @@ fn(b._h, buf, 16)
 t = b.timings()
 names = ["topup", "fast", "slow", "chunks", "fast_chunks", "redos", "pair_chunks", "pair_redos"]
 out = {"streams": n, "walk_ms": t.walk_ms, "decode_ms": t.decode_ms}
+if arg.startswith("edges:"):
+    out["model"] = model
 for k, base in (("walk", 0), ("decode", 8)):
     v = [buf[base + i] for i in range(8)]
     ch = max(1, v[3])
