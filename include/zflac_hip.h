@@ -295,6 +295,60 @@ uint64_t zflac_hip_resampled_frames(uint64_t n_frames, uint32_t rate_in, uint32_
  * floats it holds now (either pointer may be NULL). */
 int zflac_hip_batch_resample_tables(zflac_batch *b, uint64_t *built, uint64_t *held_floats);
 
+/* ---- channel mixing in the dense exports -------------------------------------------- */
+/* zflac_hip_batch_export and zflac_hip_batch_export_resampled with the channels of each stream
+ * mixed on the device by a matrix chosen by the stream's channel count, so that a batch of mono,
+ * stereo and multichannel streams becomes one tensor of C channels (a mono downmix, a stereo
+ * fold-down) in the same one launch (k_export_mixed, k_resample_mixed). */
+#define ZFLAC_MIX_MAX_CHANNELS 8
+typedef struct zflac_mix_desc {
+    uint32_t size;      /* sizeof(zflac_mix_desc): 72 on LP64 */
+    uint32_t reserved;  /* must be 0 */
+    /* matrix[n - 1]: how streams of n channels are mixed: a host array of C x n floats,
+     * row-major (m[c * n + j] = weight of source channel j in output channel c), or NULL:
+     * such streams take the plain export's fit rule */
+    const float *matrix[8];
+} zflac_mix_desc;
+/* What stays as in the unmixed call of the same kind (zflac_hip_batch_export for _export_mixed,
+ * zflac_hip_batch_export_resampled for _export_resampled_mixed): the destination, the stream
+ * semantics, starts, the zero fill, error rows, "every element written" and valid_frames.
+ * mix == NULL, or a mix whose eight pointers are all NULL, is that unmixed call in every respect:
+ * the same bits, ZFLAC_EXPORT_I32 allowed (plain export), the same errors, the same kernel. A row
+ * whose stream has n channels with matrix[n - 1] == NULL has the unmixed call's bits, also when
+ * other rows of the same call are mixed.
+ *
+ * Plain export of a mixed row (a stream whose result is OK, of n channels, matrix[n - 1] == m):
+ * output channel c of frame t is v_c[t], computed in f32 as
+ *   acc = +0; for j = 0 .. n - 1: acc = fmaf(m[c * n + j], x_j[t], acc)
+ * with x_j[t] the sample as ZFLAC_EXPORT_F32 has it; v_c[t] is then rounded to f16 or bf16
+ * exactly as the plain export rounds its f32 value. Frames past the stream's end are +0.
+ *
+ * Resampled export of a mixed row: mix, then filter. The filter of
+ * zflac_hip_batch_export_resampled runs with v_c in place of x,
+ *   y_c[m] = sum_{k < K} h[r][k] * v_c[q - W + k],
+ * v_c zero outside the stream, the sum with fused multiply-adds in ascending k as there, so a
+ * frame's value still does not depend on the window or tile it falls in. (Mixing and filtering
+ * are both linear: a mono consumer pays for one filtered channel, not two.) A stream already at
+ * the target rate is not filtered: its row has zflac_hip_batch_export_mixed's bits.
+ *
+ * Coefficients: every coefficient is 0, or finite with 2^-64 <= |m| <= 2^64. With |x| a multiple
+ * of 2^-31 and at most 1, no product or partial sum is then subnormal or -0, so leaving out a zero
+ * coefficient, or taking a coefficient of 1 as a copy, gives the same bits as the fmaf chain: a
+ * kernel may do either. An output channel whose row of m is all zeros is +0 (0x00000000) in every
+ * frame, as if it were never filtered. All non-NULL matrices are read and checked before the call
+ * returns: the caller may free or overwrite them as soon as it returns, also when `stream` is the
+ * caller's own.
+ *
+ * ZFLAC_E_INVALID_ARGUMENT (nothing written or enqueued): whatever the unmixed call rejects;
+ * mix->size != sizeof(zflac_mix_desc); reserved != 0; a non-NULL matrix together with
+ * ZFLAC_EXPORT_I32 (float dtypes only); a non-NULL matrix with channels > 8; a coefficient outside
+ * the rule above in any non-NULL matrix, whether or not a stream of that channel count is in the
+ * batch. zflac_hip_batch_export_ms reports the last synchronous export of any of the four kinds. */
+int zflac_hip_batch_export_mixed(zflac_batch *b, const zflac_export_desc *d, const zflac_mix_desc *mix,
+                                 void *dst_device, size_t dst_bytes, uint64_t *valid_frames, void *stream);
+int zflac_hip_batch_export_resampled_mixed(zflac_batch *b, const zflac_resample_desc *d, const zflac_mix_desc *mix,
+                                           void *dst_device, size_t dst_bytes, uint64_t *valid_frames, void *stream);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -349,7 +403,8 @@ const char *zflac_hip_build_id(void);
  *    zflac_hip_batch_export, zflac_hip_batch_export_ms, ZFLAC_EXPORT_*, ZFLAC_LAYOUT_*;
  *    zflac_resample_desc, zflac_hip_batch_export_resampled, zflac_hip_resampled_frames,
  *    zflac_hip_batch_resample_tables; zflac_hip_batch_decode_buckets, ZFLAC_BUCKET_*;
- *    zflac_hip_batch_front, ZFLAC_FRONT_*, ZFLAC_FLAG_FRONT_*. */
+ *    zflac_hip_batch_front, ZFLAC_FRONT_*, ZFLAC_FLAG_FRONT_*; zflac_mix_desc,
+ *    ZFLAC_MIX_MAX_CHANNELS, zflac_hip_batch_export_mixed, zflac_hip_batch_export_resampled_mixed. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -22,7 +22,15 @@ each variant is also timed by the library's own HIP events around the table copy
 times the resampled export (k_resample) instead: the same shard (44.1 kHz) to --rate, planar f32
 and planar f16, alternating in every iteration with the plain planar-f32 export (k_export) as
 the yardstick, by the same two clocks. It also writes down what the kernel as built reads
-from LDS for that many output frames, for comparison with the time."""
+from LDS for that many output frames, for comparison with the time.
+
+    python tools/bench_export.py --mixed [--resampled] [--out profiles/mix_bench.json]
+
+times the mixed export to mono (k_export_mixed, or with --resampled k_resample_mixed to --rate:
+planar f32, C = 1, the "mono" matrix) against what a user writes without it, alternating in every
+iteration: the unmixed planar-f32 export at C = 2, and that export followed by
+x.mean(1, keepdim=True). Both clocks as above (the torch mean has only the first). The result goes
+under the key "plain" or "resampled" of the output file, beside what the other run left there."""
 from __future__ import annotations
 
 import argparse
@@ -51,9 +59,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--resampled", action="store_true", help="time k_resample beside k_export planar f32")
     ap.add_argument("--rate", type=int, default=16000, help="--resampled: the target rate")
+    ap.add_argument("--mixed", action="store_true", help="time the mono mix beside the unmixed C = 2 export (+ torch mean)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "resample_bench.json" if a.resampled else "export_bench.json")
+        a.out = os.path.join(ROOT, "profiles", "mix_bench.json" if a.mixed else
+                             "resample_bench.json" if a.resampled else "export_bench.json")
     assert a.iters >= 50, "at least 50 timed exports per variant"
 
     streams = bench.make_shard(0, 1, a.streams)
@@ -66,6 +76,8 @@ def main():
     C = 2
     T = bench.FRAMES_PER_STREAM * 4096
     side = torch.cuda.Stream()
+    if a.mixed:
+        return mixed(a, batch, tm, side)
     if a.resampled:
         return resampled(a, batch, tm, side)
 
@@ -245,6 +257,105 @@ def resampled(a, batch, tm, side):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
+
+
+def mixed(a, batch, tm, side):
+    """The mono mix (C = 1) alternating with the unmixed C = 2 export, alone and followed by torch's
+    mean over the channels; with --resampled all three at --rate."""
+    import ctypes
+
+    import numpy as np
+
+    from zflac_amd import _lib
+
+    B = len(batch)
+    T_in = bench.FRAMES_PER_STREAM * 4096
+    fin = batch.info(0)[1].sample_rate
+    rate = a.rate if a.resampled else None
+    T = batch._L.zflac_hip_resampled_frames(T_in, fin, rate) if rate else T_in
+    kw = dict(frames=T, dtype=torch.float32, layout="planar", stream=side, sample_rate=rate)
+    with torch.cuda.stream(side):
+        out2 = torch.empty((B, 2, T), dtype=torch.float32, device="cuda")
+        out1 = torch.empty((B, 1, T), dtype=torch.float32, device="cuda")
+    side.synchronize()
+    variants = {
+        "unmixed_c2": lambda: tensor.export(batch, channels=2, out=out2, **kw)[0],
+        "unmixed_c2_torch_mean": lambda: tensor.export(batch, channels=2, out=out2, **kw)[0].mean(1, keepdim=True),
+        "mixed_mono": lambda: tensor.export(batch, channels=1, out=out1, mix="mono", **kw)[0],
+    }
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(side)
+        r = fn()
+        e1.record(side)
+        side.synchronize()
+        return e0.elapsed_time(e1), r
+
+    times = {k: [] for k in variants}
+    last = {}
+    with torch.cuda.stream(side):
+        for it in range(a.warmup + a.iters):
+            for name, fn in variants.items():
+                ms, last[name] = timed(fn)
+                if it >= a.warmup:
+                    times[name].append(ms)
+        diff = float((last["mixed_mono"] - last["unmixed_c2_torch_mean"]).abs().max().item())
+    # the device side alone: synchronous exports through the C calls, the library's own HIP events
+    half = np.full((1, 2), 0.5, dtype=np.float32)
+    mix = _lib.zflac_mix_desc(ctypes.sizeof(_lib.zflac_mix_desc), 0)
+    mix.matrix[1] = half.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    device_ms = {"unmixed_c2": [], "mixed_mono": []}
+    ms = ctypes.c_double()
+    for it in range(a.warmup + a.iters):
+        for name, (o, C, m) in {"unmixed_c2": (out2, 2, None), "mixed_mono": (out1, 1, ctypes.byref(mix))}.items():
+            if rate:
+                d = _lib.zflac_resample_desc(ctypes.sizeof(_lib.zflac_resample_desc), _lib.EXPORT_F32, _lib.LAYOUT_PLANAR,
+                                             C, T, None, rate, 16, 0, 0.85, 8.555504641634386)
+                rc = batch._L.zflac_hip_batch_export_resampled_mixed(batch._h, ctypes.byref(d), m, o.data_ptr(),
+                                                                     o.numel() * 4, None, None)
+            else:
+                d = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), _lib.EXPORT_F32, _lib.LAYOUT_PLANAR, C, T,
+                                           None)
+                rc = batch._L.zflac_hip_batch_export_mixed(batch._h, ctypes.byref(d), m, o.data_ptr(), o.numel() * 4,
+                                                           None, None)
+            assert rc == 0 and batch._L.zflac_hip_batch_export_ms(batch._h, ctypes.byref(ms)) == 0
+            if it >= a.warmup:
+                device_ms[name].append(ms.value)
+
+    def stats(ts):
+        return {"min_ms": min(ts), "median_ms": statistics.median(ts), "max_ms": max(ts)}
+
+    res = {"build_id": zflac_amd.build_id(), "device": torch.cuda.get_device_name(0), "streams": B, "frames_in": T_in,
+           "rate_in": fin, "rate_out": rate or fin, "frames_out": T, "iters": a.iters, "warmup": a.warmup,
+           "max_abs_mixed_minus_torch_mean": diff, "variants": {}}
+    for name in variants:
+        res["variants"][name] = stats(times[name])
+        if name in device_ms:
+            res["variants"][name]["device"] = stats(device_ms[name])
+    v = res["variants"]
+    for clock, get in (("torch_events", lambda x: x), ("device", lambda x: x["device"])):
+        u, m = get(v["unmixed_c2"]), get(v["mixed_mono"])
+        res[clock] = {"mixed_over_unmixed_c2": m["median_ms"] / u["median_ms"],
+                      "unmixed_c2_spread_ms": u["max_ms"] - u["min_ms"],
+                      "mixed_below_unmixed_by_more_than_its_spread":
+                          u["median_ms"] - m["median_ms"] > u["max_ms"] - u["min_ms"]}
+    res["torch_events"]["mixed_over_unmixed_c2_torch_mean"] = (v["mixed_mono"]["median_ms"] /
+                                                               v["unmixed_c2_torch_mean"]["median_ms"])
+    res["floor"] = ("half the multiply-adds and half the staged span" if rate else
+                    "two thirds of the bytes: (4 + 4) / (4 + 8) per frame of 16-bit stereo")
+    batch.close()
+    whole = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            whole = json.load(f)
+    whole["resampled" if rate else "plain"] = res
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(whole, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
     return 0

@@ -45,6 +45,11 @@ class zflac_resample_desc(ctypes.Structure):
                 ("rolloff", ctypes.c_double), ("beta", ctypes.c_double)]
 
 
+class zflac_mix_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("matrix", ctypes.POINTER(ctypes.c_float) * 8)]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -72,6 +77,12 @@ SIGNATURES = {
     "zflac_hip_batch_export_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double)]),
     "zflac_hip_batch_export_resampled": (ctypes.c_int, [_P, ctypes.POINTER(zflac_resample_desc), _P, ctypes.c_size_t,
                                                         ctypes.POINTER(ctypes.c_uint64), _P]),
+    "zflac_hip_batch_export_mixed": (ctypes.c_int, [_P, ctypes.POINTER(zflac_export_desc),
+                                                    ctypes.POINTER(zflac_mix_desc), _P, ctypes.c_size_t,
+                                                    ctypes.POINTER(ctypes.c_uint64), _P]),
+    "zflac_hip_batch_export_resampled_mixed": (ctypes.c_int, [_P, ctypes.POINTER(zflac_resample_desc),
+                                                              ctypes.POINTER(zflac_mix_desc), _P, ctypes.c_size_t,
+                                                              ctypes.POINTER(ctypes.c_uint64), _P]),
     "zflac_hip_resampled_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "zflac_hip_batch_resample_tables": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64),
                                                        ctypes.POINTER(ctypes.c_uint64)]),
@@ -101,6 +112,7 @@ EXPORT_BF16 = 2
 EXPORT_I32 = 3
 LAYOUT_PLANAR = 0
 LAYOUT_INTERLEAVED = 1
+MIX_MAX_CHANNELS = 8  # zflac_mix_desc: C and n of a matrix, at most
 # zflac_hip_batch_decode_buckets: one bit per k_decode history bucket (ZFLAC_BUCKET_*)
 BUCKET_8 = 1
 BUCKET_4 = 2

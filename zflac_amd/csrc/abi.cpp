@@ -1,5 +1,6 @@
 // abi.cpp -- the extern "C" ABI of include/zflac_hip.h over the host units (batch.h), the
 // batch's destructor, the build id, and the entry points of the diagnostic builds.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -84,12 +85,51 @@ ExportRow export_row(const StreamState& s, uint64_t start) {
     return r;
 }
 
+// The matrices of a mixed export, checked and laid out as the kernels read them: at[n] is where
+// the C x n matrix of the n-channel streams starts in `table` (0: none, the fit rule), table[0] is
+// unused. any: the call has a matrix and launches the mixed kernel.
+struct MixPlan {
+    bool any = false;
+    uint16_t at[MIX_MAX_CH + 1] = {};
+    std::vector<float> table;
+};
+
+// zflac_mix_desc's rules (mix may be NULL). Every non-NULL matrix is read here, so the caller may
+// free it when the call returns.
+bool mix_plan(const zflac_mix_desc* mix, int dtype, uint64_t channels, MixPlan& p) {
+    if (!mix) return true;
+    if (mix->size != sizeof(zflac_mix_desc) || mix->reserved) return false;
+    static_assert(ZFLAC_MIX_MAX_CHANNELS == MIX_MAX_CH, "zflac_hip.h and common.h disagree");
+    for (uint32_t n = 1; n <= MIX_MAX_CH; n++) {
+        const float* m = mix->matrix[n - 1];
+        if (!m) continue;
+        if (dtype == ZFLAC_EXPORT_I32 || channels > MIX_MAX_CH) return false;
+        if (!p.any) p.table.assign(1, 0.0f);
+        p.any = true;
+        p.at[n] = (uint16_t)p.table.size();
+        for (uint64_t i = 0; i < channels * n; i++) {
+            const float a = std::fabs(m[i]);  // (NaN fails the range test)
+            if (a != 0.0f && !(a >= 0x1p-64f && a <= 0x1p64f)) return false;
+            p.table.push_back(a == 0.0f ? 0.0f : m[i]);
+        }
+    }
+    return true;
+}
+
+// ExportRow::mix of a stream of nch channels
+uint16_t mix_at(const MixPlan& p, uint32_t nch) { return nch <= MIX_MAX_CH ? p.at[nch] : 0; }
+
+// bytes of n row records with the coefficient table behind them (16-byte aligned)
+size_t mix_table_offset(size_t row_bytes) { return (row_bytes + 15) & ~(size_t)15; }
+
 // Before the row records are written: the buffers exist and the last export has let go of them.
 // Returns whether this export is timed.
 bool export_begin(zflac_batch* b, size_t n, void* stream, hipStream_t st) {
     if (!b->exp_pin) {
-        ck(hipHostMalloc(reinterpret_cast<void**>(&b->exp_pin), n * sizeof(ResampleRow), hipHostMallocDefault));
-        b->exp_rows.alloc(n * sizeof(ResampleRow));
+        // room for the larger record and for a mixed export's coefficient table behind the records
+        const size_t bytes = mix_table_offset(n * sizeof(ResampleRow)) + MIX_TABLE_FLOATS * sizeof(float);
+        ck(hipHostMalloc(reinterpret_cast<void**>(&b->exp_pin), bytes, hipHostMallocDefault));
+        b->exp_rows.alloc(bytes);
         ck(hipEventCreateWithFlags(&b->ev_exp_copy, hipEventDisableTiming));
         ck(hipEventCreateWithFlags(&b->ev_exp, hipEventDisableTiming));
     }
@@ -102,6 +142,19 @@ bool export_begin(zflac_batch* b, size_t n, void* stream, hipStream_t st) {
         for (auto& e : b->ev_exp_t)
             if (!e) ck(hipEventCreate(&e));
     return timed;
+}
+
+// After the row records (row_bytes of them) are in exp_pin: the coefficient table goes behind
+// them, so that one copy takes both. Returns the table's device address (null without a matrix)
+// and grows `bytes`, what export_run copies.
+const float* mix_stage(zflac_batch* b, const MixPlan& p, size_t row_bytes, size_t& bytes) {
+    bytes = row_bytes;
+    if (!p.any) return nullptr;
+    const size_t at = mix_table_offset(row_bytes);
+    std::memset(b->exp_pin + row_bytes, 0, at - row_bytes);
+    std::memcpy(b->exp_pin + at, p.table.data(), p.table.size() * sizeof(float));
+    bytes = at + p.table.size() * sizeof(float);
+    return reinterpret_cast<const float*>(b->exp_rows.p + at);
 }
 
 // The records are in exp_pin: copy them, launch, and finish as the caller's stream asks.
@@ -335,12 +388,19 @@ int zflac_hip_batch_timings_ex(zflac_batch* b, zflac_timings* t, size_t size) {
 
 int zflac_hip_abi_version(void) { return ZFLAC_HIP_ABI_VERSION; }
 
-int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst_device, size_t dst_bytes,
-                           uint64_t* valid_frames, void* stream) {
+// zflac_hip_batch_export (mix == NULL) and zflac_hip_batch_export_mixed
+static int export_plain(zflac_batch* b, const zflac_export_desc* d, const zflac_mix_desc* mix, void* dst_device,
+                        size_t dst_bytes, uint64_t* valid_frames, void* stream) {
     ExportShape s;
+    MixPlan mp;
     if (!d || !export_shape(b, d->size, sizeof(zflac_export_desc), d->dtype, ZFLAC_EXPORT_I32, d->layout, d->channels,
                             d->frames, dst_device, dst_bytes, s))
         return E_INVALID_ARGUMENT;
+    try {
+        if (!mix_plan(mix, d->dtype, s.C, mp)) return E_INVALID_ARGUMENT;
+    } catch (const std::bad_alloc&) {
+        return E_OUT_OF_MEMORY;
+    }
     const size_t n = s.n;
     for (size_t i = 0; valid_frames && i < n; i++) {
         const StreamState& st = b->streams[i];
@@ -354,7 +414,12 @@ int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->stream;
         const bool timed = export_begin(b, n, stream, st);
         ExportRow* rows = reinterpret_cast<ExportRow*>(b->exp_pin);
-        for (size_t i = 0; i < n; i++) rows[i] = export_row(b->streams[i], d->starts ? d->starts[i] : 0);
+        for (size_t i = 0; i < n; i++) {
+            rows[i] = export_row(b->streams[i], d->starts ? d->starts[i] : 0);
+            rows[i].mix = mix_at(mp, rows[i].nch);
+        }
+        size_t bytes;
+        const float* coef = mix_stage(b, mp, n * sizeof(ExportRow), bytes);
         ExportArgs a;
         std::memset(&a, 0, sizeof(a));
         a.rows = reinterpret_cast<const ExportRow*>(b->exp_rows.p);
@@ -364,8 +429,9 @@ int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst
         a.n_rows = (uint32_t)n;
         a.tiles = (uint32_t)s.tiles;
         a.vec = s.vec;
-        export_run(b, n * sizeof(ExportRow), timed, stream, st,
-                   [&] { return launch_export(d->dtype, d->layout, a, st); });
+        export_run(b, bytes, timed, stream, st, [&] {  // without a matrix: k_export, as ever
+            return coef ? launch_export_mixed(d->dtype, d->layout, a, coef, st) : launch_export(d->dtype, d->layout, a, st);
+        });
     } catch (const DeviceError&) {
         return E_DEVICE;
     } catch (const std::bad_alloc&) {
@@ -374,19 +440,40 @@ int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst
     return E_OK;
 }
 
+int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst_device, size_t dst_bytes,
+                           uint64_t* valid_frames, void* stream) {
+    return export_plain(b, d, nullptr, dst_device, dst_bytes, valid_frames, stream);
+}
+
+int zflac_hip_batch_export_mixed(zflac_batch* b, const zflac_export_desc* d, const zflac_mix_desc* mix,
+                                 void* dst_device, size_t dst_bytes, uint64_t* valid_frames, void* stream) {
+    return export_plain(b, d, mix, dst_device, dst_bytes, valid_frames, stream);
+}
+
 uint64_t zflac_hip_resampled_frames(uint64_t n_frames, uint32_t rate_in, uint32_t rate_out) {
     return resampled_frames(n_frames, rate_in, rate_out);
 }
 
-int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* d, void* dst_device, size_t dst_bytes,
-                                     uint64_t* valid_frames, void* stream) {
+// zflac_hip_batch_export_resampled (mix == NULL) and zflac_hip_batch_export_resampled_mixed
+static int export_resampled(zflac_batch* b, const zflac_resample_desc* d, const zflac_mix_desc* mix, void* dst_device,
+                            size_t dst_bytes, uint64_t* valid_frames, void* stream) {
     ExportShape s;
+    MixPlan mp;
     if (!d || !export_shape(b, d->size, sizeof(zflac_resample_desc), d->dtype, ZFLAC_EXPORT_BF16, d->layout,
                             d->channels, d->frames, dst_device, dst_bytes, s))
         return E_INVALID_ARGUMENT;
     if (!d->sample_rate || d->sample_rate > RESAMPLE_MAX_RATE || d->reserved ||
         !resample_params_ok(d->zeros, d->rolloff, d->beta))
         return E_INVALID_ARGUMENT;
+    try {
+        if (!mix_plan(mix, d->dtype, s.C, mp)) return E_INVALID_ARGUMENT;
+    } catch (const std::bad_alloc&) {
+        return E_OUT_OF_MEMORY;
+    }
+    // channels of stream `st` that k_resample stages: min(its own, C), or C when it is mixed first
+    auto staged = [&](const StreamState& st) {
+        return mix_at(mp, st.info.channels) ? s.C : std::min<uint64_t>(st.info.channels, s.C);
+    };
     const size_t n = s.n;
     // What each row takes, before anything is written or enqueued. plan[i] < 0: k_export's
     // paths (same rate, error, rate 0); else the index of the row's ratio in `ratios`.
@@ -421,7 +508,7 @@ int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* 
                 needs.push_back(nd);
             }
             plan[i] = k;
-            const ResampleTile rt = resample_tile(needs[k].ratio, std::min<uint64_t>(st.info.channels, s.C));
+            const ResampleTile rt = resample_tile(needs[k].ratio, (uint32_t)staged(st));
             tiles = std::max(tiles, (s.T + rt.tile - 1) / rt.tile);
         }
     } catch (const std::bad_alloc&) {
@@ -463,7 +550,7 @@ int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* 
                 if (!n_out[i]) r.e.src = nullptr;  // a stream whose rate is 0: a zero row
             } else {
                 const ResampleTable* t = tabs[plan[i]];
-                const ResampleTile rt = resample_tile(t->ratio, std::min<uint64_t>(ss.info.channels, s.C));
+                const ResampleTile rt = resample_tile(t->ratio, (uint32_t)staged(ss));
                 r.e = export_row(ss, 0);  // (src by the source's length ...)
                 r.e.start = start;        // ... the window by the resampled stream's)
                 r.n_out = n_out[i];
@@ -480,8 +567,11 @@ int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* 
                     r.e.src = nullptr;  // no frames, or the window is past the end: a zero row
                 }
             }
+            r.e.mix = mix_at(mp, r.e.nch);
             rows[i] = r;
         }
+        size_t bytes;
+        const float* coef = mix_stage(b, mp, n * sizeof(ResampleRow), bytes);
         ResampleArgs a;
         std::memset(&a, 0, sizeof(a));
         a.rows = reinterpret_cast<const ResampleRow*>(b->exp_rows.p);
@@ -491,14 +581,26 @@ int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* 
         a.n_rows = (uint32_t)n;
         a.tiles = (uint32_t)tiles;
         a.vec = s.vec;
-        export_run(b, n * sizeof(ResampleRow), timed, stream, st,
-                   [&] { return launch_resample(d->dtype, d->layout, a, st); });
+        export_run(b, bytes, timed, stream, st, [&] {  // without a matrix: k_resample, as ever
+            return coef ? launch_resample_mixed(d->dtype, d->layout, a, coef, st)
+                        : launch_resample(d->dtype, d->layout, a, st);
+        });
     } catch (const DeviceError&) {
         return E_DEVICE;
     } catch (const std::bad_alloc&) {
         return E_OUT_OF_MEMORY;
     }
     return E_OK;
+}
+
+int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* d, void* dst_device, size_t dst_bytes,
+                                     uint64_t* valid_frames, void* stream) {
+    return export_resampled(b, d, nullptr, dst_device, dst_bytes, valid_frames, stream);
+}
+
+int zflac_hip_batch_export_resampled_mixed(zflac_batch* b, const zflac_resample_desc* d, const zflac_mix_desc* mix,
+                                           void* dst_device, size_t dst_bytes, uint64_t* valid_frames, void* stream) {
+    return export_resampled(b, d, mix, dst_device, dst_bytes, valid_frames, stream);
 }
 
 int zflac_hip_batch_resample_tables(zflac_batch* b, uint64_t* built, uint64_t* held_floats) {

@@ -303,7 +303,9 @@ struct ExportRow {
     uint64_t start;     // first frame of the window (< n_frames when src != nullptr)
     uint8_t nch;        // channels of the stream
     uint8_t kind;       // ZFLAC_S8 / ZFLAC_S16 / ZFLAC_S32 container
-    uint8_t pad_[6];
+    uint16_t mix;       // the mixed exports: where the row's matrix (C x nch floats, row-major) starts in
+                        // the call's coefficient table, in floats; 0 = none (the fit rule)
+    uint8_t pad_[4];
 };
 static_assert(sizeof(ExportRow) == 32, "ExportRow is the 32-byte record host and kernel share");
 
@@ -320,6 +322,12 @@ struct ExportArgs {
     uint32_t tiles;        // tiles per row: ceil(T / EXPORT_TILE); grid = n_rows * tiles
     uint32_t vec;          // dst and its rows are 16-byte aligned: the 16-byte store paths apply
 };
+
+// The coefficient table of a mixed export (k_export_mixed, k_resample_mixed): float 0 is unused
+// (offset 0 means "no matrix"), then one C x n matrix for every channel count n = 1..8 that has
+// one: at most 1 + 36 * 8 floats. It lies behind the row records in the same device buffer.
+constexpr uint32_t MIX_MAX_CH = 8;  // C and n of a matrix, at most
+constexpr uint32_t MIX_TABLE_FLOATS = 1 + 36 * MIX_MAX_CH;
 
 // k_resample (resample.hip): one row of the resampled dense destination. `e` is the row as
 // k_export sees it, with e.start and the window counted in frames of the RESAMPLED stream and

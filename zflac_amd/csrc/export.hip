@@ -28,6 +28,11 @@
 // stream's end loads element by element under a bound, so nothing past the last sample of a
 // stream is ever read. No LDS, no scratch; all element offsets are 64-bit. The device code is
 // in export_tile.h, which k_resample (resample.hip) shares for the rows it does not filter.
+//
+// k_export_mixed is the kernel of zflac_hip_batch_export_mixed: the same grid and the same row
+// records, with the call's coefficient table as a second argument. A row whose record names a
+// matrix (ExportRow::mix) takes mix_tile() (mix_tile.h), every other row export_tile() as above.
+// k_export itself knows nothing of matrices: the unmixed call launches it as before.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -36,6 +41,7 @@
 #include "common.h"
 #include "export_tile.h"
 #include "launch.h"
+#include "mix_tile.h"
 
 namespace zflac {
 namespace {
@@ -49,6 +55,27 @@ __global__ __launch_bounds__(EXPORT_THREADS) void k_export(ExportArgs a) {
     const ExportRow r = a.rows[row_i];
     OT* row = static_cast<OT*>(a.dst) + (uint64_t)row_i * a.channels * a.frames;
     export_tile<DT, LAYOUT>(row, r, a.channels, a.frames, a.vec, (uint64_t)tile * EXPORT_TILE);
+}
+
+template <int DT, int LAYOUT>
+__global__ __launch_bounds__(EXPORT_THREADS) void k_export_mixed(ExportArgs a, const float* coef) {
+    using OT = typename Out<DT>::T;
+    const uint32_t row_i = blockIdx.x / a.tiles;
+    const uint32_t tile = blockIdx.x - row_i * a.tiles;
+    if (row_i >= a.n_rows) return;
+    const ExportRow r = a.rows[row_i];
+    OT* row = static_cast<OT*>(a.dst) + (uint64_t)row_i * a.channels * a.frames;
+    if (r.mix) mix_tile<DT, LAYOUT>(row, r, coef, a.channels, a.frames, a.vec, (uint64_t)tile * EXPORT_TILE);
+    else export_tile<DT, LAYOUT>(row, r, a.channels, a.frames, a.vec, (uint64_t)tile * EXPORT_TILE);
+}
+
+template <int DT>
+hipError_t launch_mixed_dt(int layout, const ExportArgs& a, const float* coef, uint32_t blocks, hipStream_t st) {
+    if (layout == ZFLAC_LAYOUT_PLANAR)
+        hipLaunchKernelGGL((k_export_mixed<DT, ZFLAC_LAYOUT_PLANAR>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a, coef);
+    else
+        hipLaunchKernelGGL((k_export_mixed<DT, ZFLAC_LAYOUT_INTERLEAVED>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a, coef);
+    return hipGetLastError();
 }
 
 template <int DT>
@@ -71,6 +98,18 @@ hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t
         case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16>(layout, a, blocks, st);
         case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16>(layout, a, blocks, st);
         default: return launch_dt<ZFLAC_EXPORT_I32>(layout, a, blocks, st);
+    }
+}
+
+// the same grid; dtype is F32, F16 or BF16, a.channels at most MIX_MAX_CH, coef the call's table
+hipError_t launch_export_mixed(int dtype, int layout, const ExportArgs& a, const float* coef, hipStream_t st) {
+    const uint32_t blocks = a.n_rows * a.tiles;
+    if (blocks == 0) return hipSuccess;
+    switch (dtype) {
+        case ZFLAC_EXPORT_F32: return launch_mixed_dt<ZFLAC_EXPORT_F32>(layout, a, coef, blocks, st);
+        case ZFLAC_EXPORT_F16: return launch_mixed_dt<ZFLAC_EXPORT_F16>(layout, a, coef, blocks, st);
+        case ZFLAC_EXPORT_BF16: return launch_mixed_dt<ZFLAC_EXPORT_BF16>(layout, a, coef, blocks, st);
+        default: return hipErrorInvalidValue;
     }
 }
 

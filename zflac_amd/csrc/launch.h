@@ -46,8 +46,11 @@ hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode);
 
 // export.hip
 hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st);
+// k_export_mixed: coef is the call's coefficient table (MIX_TABLE_FLOATS floats at most) on the device
+hipError_t launch_export_mixed(int dtype, int layout, const ExportArgs& a, const float* coef, hipStream_t st);
 
 // resample.hip
 hipError_t launch_resample(int dtype, int layout, const ResampleArgs& a, hipStream_t st);
+hipError_t launch_resample_mixed(int dtype, int layout, const ResampleArgs& a, const float* coef, hipStream_t st);
 
 }  // namespace zflac

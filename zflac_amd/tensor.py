@@ -1,5 +1,6 @@
 """Decoded batches as dense torch tensors on the GPU (zflac_hip_batch_export, k_export; at one
-sample rate with sample_rate=: zflac_hip_batch_export_resampled, k_resample).
+sample rate with sample_rate=: zflac_hip_batch_export_resampled, k_resample; with the channels
+mixed on the device with mix=: zflac_hip_batch_export_mixed / _export_resampled_mixed).
 
     import torch                      # before zflac_amd loads its library (see below)
     from zflac_amd import Batch, tensor
@@ -84,9 +85,61 @@ def check_single_runtime() -> None:
     _checked_at = now
 
 
+def mix_preset(name: str) -> dict:
+    """The matrices `mix="mono"` and `mix="stereo"` stand for: {n: [channels][n] float32 weights}
+    for streams of n channels, as nested lists of numpy.float32 values in FLAC's channel order.
+    Pure Python, no GPU.
+
+    "mono" (channels = 1): n = 2..8 average their channels, one row of float32(1/n); mono streams
+    have no matrix (the plain export's row).
+    "stereo" (channels = 2), a = float32(sqrt(0.5)): a mono stream goes to both outputs with weight
+    1; stereo streams have no matrix; 3..8 channels fold down to left / right: the front pair with
+    weight 1, centre, back and side channels of the same side with a (the back centre of 7
+    channels with 0.5 to both), LFE dropped. Nothing is normalised: a sum may exceed 1.0."""
+    import numpy as np
+
+    f = np.float32
+    if name == "mono":
+        return {n: [[f(1.0 / n)] * n] for n in range(2, 9)}
+    if name == "stereo":
+        a, o, z, h = f(np.sqrt(0.5)), f(1.0), f(0.0), f(0.5)
+        return {
+            1: [[o], [o]],
+            3: [[o, z, a], [z, o, a]],                                  # L R C
+            4: [[o, z, a, z], [z, o, z, a]],                            # FL FR BL BR
+            5: [[o, z, a, a, z], [z, o, a, z, a]],                      # FL FR FC BL BR
+            6: [[o, z, a, z, a, z], [z, o, a, z, z, a]],                # FL FR FC LFE BL BR
+            7: [[o, z, a, z, h, a, z], [z, o, a, z, h, z, a]],          # FL FR FC LFE BC SL SR
+            8: [[o, z, a, z, a, z, a, z], [z, o, a, z, z, a, z, a]],    # FL FR FC LFE BL BR SL SR
+        }
+    raise ValueError(f"unknown mix preset {name!r}: 'mono' or 'stereo'")
+
+
+_PRESET_CHANNELS = {"mono": 1, "stereo": 2}
+
+
+def _mix_desc(mix, channels):
+    """zflac_mix_desc of `mix` (a dict {n: [channels, n] array-like}) and the arrays it points to."""
+    import numpy as np
+
+    if channels > _lib.MIX_MAX_CHANNELS:
+        raise ValueError(f"a mix takes channels <= {_lib.MIX_MAX_CHANNELS}")
+    desc = _lib.zflac_mix_desc(ctypes.sizeof(_lib.zflac_mix_desc), 0)
+    keep = []
+    for n, m in mix.items():
+        if not isinstance(n, int) or not 1 <= n <= _lib.MIX_MAX_CHANNELS:
+            raise ValueError(f"mix: channel counts are 1..{_lib.MIX_MAX_CHANNELS}, not {n!r}")
+        arr = np.ascontiguousarray(m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else m, dtype=np.float32)
+        if arr.shape != (channels, n):
+            raise ValueError(f"mix[{n}] has shape {arr.shape}, expected {(channels, n)}")
+        keep.append(arr)
+        desc.matrix[n - 1] = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    return desc, keep
+
+
 def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.float32, layout="planar", out=None,
            stream=None, sample_rate=None, resample_zeros=16, resample_rolloff=0.85,
-           resample_beta=8.555504641634386):
+           resample_beta=8.555504641634386, mix=None):
     """The last run of `batch` as one dense tensor -> (tensor, lengths).
 
     tensor: [B, channels, frames] (layout="planar") or [B, frames, channels] ("interleaved") of
@@ -102,10 +155,30 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
     k_resample: a Kaiser-windowed sinc of `resample_zeros` zero crossings a side, cutoff
     `resample_rolloff` of the lower Nyquist rate, window shape `resample_beta`), so that streams of
     any rates share one time base. frames, starts and lengths then count frames at sample_rate,
-    and dtype is a float type. A stream already at sample_rate is exported as without it."""
+    and dtype is a float type. A stream already at sample_rate is exported as without it.
+
+    mix: the channels of each stream mixed on the device (zflac_hip_batch_export_mixed; with
+    sample_rate, mixed first and then filtered). A dict {n: array-like [channels, n]}: streams of n
+    channels get output channel c = sum_j mix[n][c][j] * source channel j (f32, fused
+    multiply-adds in ascending j); channel counts not in the dict keep the fit rule above.
+    Coefficients are 0 or 2^-64 <= |m| <= 2^64, channels <= 8, dtype a float type. Or "mono" /
+    "stereo": mix_preset(name), with channels defaulting to (and required to be) 1 / 2. The
+    presets do not normalise: a "stereo" sum may exceed 1.0."""
     check_single_runtime()
     if dtype not in _DTYPES:
         raise TypeError(f"dtype must be one of {sorted(map(str, _DTYPES))}")
+    if mix is not None:
+        if dtype == torch.int32:
+            raise TypeError("a mixed export is float32, float16 or bfloat16")
+        if isinstance(mix, str):
+            preset = mix_preset(mix)
+            if channels is None:
+                channels = _PRESET_CHANNELS[mix]
+            if int(channels) != _PRESET_CHANNELS[mix]:
+                raise ValueError(f"mix={mix!r} takes channels={_PRESET_CHANNELS[mix]}")
+            mix = preset
+        elif not isinstance(mix, dict):
+            raise TypeError("mix is a dict {n: [channels, n] weights}, 'mono' or 'stereo'")
     if sample_rate is not None:
         if dtype == torch.int32:
             raise TypeError("a resampled export is float32, float16 or bfloat16")
@@ -159,17 +232,22 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
         # stream and returns when the tensor is complete; work queued on `out` goes first
         stream.synchronize()
     valid = (ctypes.c_uint64 * max(n, 1))()
+    mix_desc, mix_arrays = _mix_desc(mix, channels) if mix is not None else (None, None)
     if sample_rate is None:
         desc = _lib.zflac_export_desc(ctypes.sizeof(_lib.zflac_export_desc), _DTYPES[dtype], _LAYOUTS[layout],
                                       channels, frames, h_starts)
-        call = batch._L.zflac_hip_batch_export
+        name = "zflac_hip_batch_export"
     else:
         desc = _lib.zflac_resample_desc(ctypes.sizeof(_lib.zflac_resample_desc), _DTYPES[dtype], _LAYOUTS[layout],
                                         channels, frames, h_starts, sample_rate, int(resample_zeros), 0,
                                         float(resample_rolloff), float(resample_beta))
-        call = batch._L.zflac_hip_batch_export_resampled
-    rc = call(batch._h, ctypes.byref(desc), out.data_ptr() or None, out.numel() * out.element_size(), valid,
-              stream.cuda_stream or None)
+        name = "zflac_hip_batch_export_resampled"
+    args = (out.data_ptr() or None, out.numel() * out.element_size(), valid, stream.cuda_stream or None)
+    if mix_desc is None:
+        rc = getattr(batch._L, name)(batch._h, ctypes.byref(desc), *args)
+    else:  # (the library has read the matrices when the call returns)
+        rc = getattr(batch._L, name + "_mixed")(batch._h, ctypes.byref(desc), ctypes.byref(mix_desc), *args)
+        del mix_arrays
     if n == 0 and rc == errors.InvalidArgument.code:
         rc = 0  # an empty tensor has no address to hand over
     errors.check(rc, "batch_export")
