@@ -2,6 +2,7 @@
 // decorrelation, the staged write-back of the 16-bit kernels, and the chunk-start top-up.
 #pragma once
 #include "lane_reader.h"
+#include "row_mask.h"
 
 namespace zflac {
 
@@ -121,8 +122,10 @@ struct Stage {
     static constexpr uint32_t ROW_FRAMES = 64u / PIECES;  // frames per write-back row
     using Mask = std::conditional_t<MONO, uint64_t, uint32_t>;
     guint4* out;     // the output buffer (wave-uniform, held in VGPRs): the pointer write-back
-    __amdgpu_buffer_rsrc_t rs;  // the same buffer as a raw resource (SGPRs): the resource write-back
-    uint32_t gq[4];  // quad index (from `out`) of this lane's piece of row t at sample 0
+    uint32_t rw[3];  // the resource write-back: the buffer's address (low, high) and bytes, wave-uniform
+                     // but held in VGPRs on purpose (see store_rsrc)
+    uint32_t gq[4];  // quad index (from `out`) of this lane's piece of row t at sample 0 (the resource
+                     // form: its byte offset)
     Mask mask;       // frames (bit j) whose staged chunk is valid: fast, not redone, writable
     uint32_t base;   // first sample of the staged chunk
     uint32_t q0;     // this wave's first quad in g_stage
@@ -158,25 +161,47 @@ struct Stage {
         }
     }
     // The same rows through the buffer resource (WB_RSRC launches: the class's output is at most
-    // WB_RSRC_MAX bytes). The offset is 32 bits, one v_add_lshl, and a masked row sets its bit 31,
-    // which lies past the resource: the buffer unit drops the store, no dummy line is written. The
-    // row's bit comes from a scalar shift of ~mask by the row's first frame, then one per-lane
-    // shift by the lane's frame within the row; v_lshl_or moves it to bit 31 and drops the rest.
-    __device__ __forceinline__ void store_rsrc(const uint4 (&v)[4]) const {
-        const uint32_t bq = MONO ? base / 8u : base / 4u;
-        const uint32_t fr = lane() / PIECES;  // this lane's frame within a row
+    // WB_RSRC_MAX = 2^31 bytes). gq[t] is then the byte offset of the lane's piece at sample 0
+    // (< 2^31, fixed for the subframe) and goes in as the store's vector offset unchanged; the
+    // chunk's own offset is wave-uniform, at most 4 * 65535 bytes, and is the store's scalar
+    // offset: their sum stays below 2^32. A lane whose frame is masked takes the offset 2^31
+    // instead, which lies past the resource with or without the scalar offset: the buffer unit
+    // drops its store, no dummy line is written. The choice is one v_cndmask per row on the row's
+    // lane mask (row_lane_mask: scalar instructions on the wave-uniform frame mask), and nothing
+    // else per lane is left in the chunk.
+    // (The four stores stay unconditional, in straight-line code. Stored under their lane masks
+    // in branches of their own (s_and_saveexec, s_cbranch_execz) they saved the four v_cndmask,
+    // but the top-up's waits for its staged loads can then no longer count on the stores as
+    // younger operations: vmcnt(7..4) became vmcnt(3..0), every chunk start waited for its own
+    // write-back to finish, and k_decode ran 4 % longer with 4 % fewer vector instructions.)
+    // The resource's four words are made here, at every write-back, from three v_readfirstlane of
+    // rw[] and a constant: held in SGPRs across the chunk they were spilled to VGPR lanes, and each
+    // of the four stores read them back and wrote them out again (8 v_readlane / v_writelane per
+    // store). The empty asm makes rw[] a new value at every write-back, so the reads stay here.
+    // `sbase`: `base` as a value the compiler knows to be wave-uniform (see flush).
+    __device__ __forceinline__ void store_rsrc(const uint4 (&v)[4], uint32_t sbase) {
+        const uint32_t so = MONO ? sbase * 2u : sbase * 4u;  // bytes per sample: 2 mono, 4 stereo
+        asm volatile("" : "+v"(rw[0]), "+v"(rw[1]), "+v"(rw[2]));
+        // (each half widened as unsigned: the builtin returns int, and a sign-extended low half
+        // would set every high bit of a pointer whose bit 31 is set)
+        const uint64_t o = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(rw[1]) << 32) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(rw[0]);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            reinterpret_cast<void*>(o), (short)0, (int)__builtin_amdgcn_readfirstlane(rw[2]), BUFFER_RSRC_WORD3);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            const uint32_t dead = (uint32_t)((Mask)~mask >> (t * (int)ROW_FRAMES)) >> fr;
-            const uint32_t off = ((gq[t] + bq) << 4) | (dead << 31);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v[t]), rs, (int)off, 0, 0);
+            const uint32_t off = __builtin_amdgcn_inverse_ballot_w64(row_lane_mask<MONO>(mask, t)) ? gq[t] : 0x80000000u;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v[t]), rs, (int)off, (int)so, 0);
         }
     }
+    // `sbase`: the staged chunk's first sample again, for the resource form's scalar offset. `base`
+    // itself is carried round the chunk loop, whose trip count is per-lane to the compiler, so it
+    // counts as divergent and a store with it as scalar offset is wrapped in a waterfall loop.
     template <bool WBR>
-    __device__ __forceinline__ void flush(uint4* dummy) {
+    __device__ __forceinline__ void flush(uint4* dummy, uint32_t sbase) {
         uint4 v[4];
         read(v);
-        if constexpr (WBR) store_rsrc(v);
+        if constexpr (WBR) store_rsrc(v, sbase);
         else store(v, dummy);
     }
 };
@@ -197,9 +222,9 @@ __device__ __forceinline__ uint32_t dummy_slot() {
 // just read every staged piece into registers (LDS operations of a wave complete in order),
 // and the chunk's own pieces are written only after this top-up.
 template <int KIND, int LAY, bool WALK, bool WBR>
-__device__ __forceinline__ void topup_st(Rdr& rd, Pend& pd, StageOf<LAY>& sg, uint4* dummy) {
+__device__ __forceinline__ void topup_st(Rdr& rd, Pend& pd, StageOf<LAY>& sg, uint4* dummy, uint32_t sbase) {
     if constexpr (!WALK) {
-        if constexpr (staged<KIND, LAY>()) sg.template flush<WBR>(dummy);
+        if constexpr (staged<KIND, LAY>()) sg.template flush<WBR>(dummy, sbase);
         else pd.flush(pend_two<KIND>());
     }
     rd.template topup<topup_quads<KIND>()>();

@@ -75,16 +75,12 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
     // (in VGPRs: as a wave-uniform kernel argument it stayed part of the 16-SGPR tuple of the
     // argument load, which the allocator spilled to VGPR lanes and restored with 16 v_readlane
     // at every chunk start's write-back)
-    // (the resource form holds four SGPRs instead: made from values read with v_readfirstlane
-    // once per subframe, which the allocator cannot fetch again from the argument tuple)
+    // (the resource form: address and size stay in VGPRs as well, Stage::store_rsrc)
     if constexpr (WBR) {
         const uint64_t o = reinterpret_cast<uintptr_t>(out);
-        // (each half widened as unsigned: the builtin returns int, and a sign-extended low half
-        // would set every high bit of a pointer whose bit 31 is set)
-        const uint64_t ou = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(o >> 32)) << 32) |
-                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)o);
-        sg.rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(ou), (short)0,
-                                                  (int)__builtin_amdgcn_readfirstlane(out_bytes), BUFFER_RSRC_WORD3);
+        sg.rw[0] = (uint32_t)o;
+        sg.rw[1] = (uint32_t)(o >> 32);
+        sg.rw[2] = out_bytes;
     } else {
         uint64_t outv = reinterpret_cast<uintptr_t>(out);
         asm volatile("" : "+v"(outv));
@@ -95,6 +91,10 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
         for (int t = 0; t < 4; t++)  // frame row_frame(t)'s output, in quads (fc.packed: < 2^32)
             sg.gq[t] = (uint32_t)__shfl((int)(uint32_t)(fc.out_elem / 8u), (int)StageOf<LAY>::row_frame(t)) +
                        (StageOf<LAY>::lane() & (StageOf<LAY>::PIECES - 1u));
+        if constexpr (WBR) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) sg.gq[t] <<= 4;  // Stage::store_rsrc takes bytes
+        }
     }
     Pred<KIND, M> pr;
     if constexpr (WALK) {
@@ -118,14 +118,42 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
     // kernels keep a fixed 8: the extra wave-uniform state measured 1-3 % slower there.
     constexpr bool BACKOFF = LAY == LAY_MONO;
     uint32_t pair_fail = 0;  // wave-uniform: pair chunks redone since the last good one
+    // The form selectors whose inputs are fixed for longer than a chunk, held as wave-uniform lane
+    // counts (s_bcnt1 of the ballot: a 32-bit scalar; a bool made from `ballot != 0` went through
+    // v_cndmask and v_readfirstlane whenever it was kept across chunks):
+    // * ms_bad (all_ms below): lanes that are not mid/side or, 16-bit, have wasted / justify
+    //   shifts. Its inputs are fixed once parse_subframe has returned, so it is taken once, over
+    //   the lanes with a subframe. Every later chunk's fast lanes are among them: a zero stays
+    //   true, and a stale non-zero (the lane has since finished) only picks the generic
+    //   decorrelation, which is correct for every channel assignment.
+    // * k_bad (fast lanes outside the pair forms' k range, or escaped) and esc_n (fast lanes
+    //   escaped) depend on L.k and L.esc, which change only in read_partition_header (at a chunk
+    //   start) and in slow_chunk. sel_stale asks for them to be taken again: set at a chunk start
+    //   where some lane read a partition header, and after every chunk that ran slow_chunk. In
+    //   between the fast lanes can only become fewer (a chunk with a lane that is active but not
+    //   fast runs slow_chunk), so a zero stays true and a non-zero is at worst conservative: one
+    //   code per step, or the escape form, which decode any k.
+    // (HOLD: the walk and the 16-bit pure kernels up to order 16. In the one-wave kernels (order
+    // 32, MIX, the larger 32-bit stereo buckets) the held counts moved 25 VGPRs to spill slots, so
+    // every other kernel takes its selectors at every chunk, over the chunk's fast lanes, as before.)
+    constexpr bool HOLD = WALK || (KIND == 1 && !MIX && M != 32);
+    auto count = [](bool p) { return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); };
+    uint32_t sel_stale = 1, k_bad = 0, esc_n = 0, ms_bad = 0;
+    if constexpr (HOLD && FormMsOne::template in_kernel<KIND, LAY, MIX, WALK>()) {
+        if constexpr (LAY == LAY_STEREO) ms_bad = count(L.mode != M_NONE && L.chan_code != 10);
+        if constexpr (KIND == 1) ms_bad += count(L.mode != M_NONE && (L.wasted != 0 || fc.justify != 0));
+    }
     ChunkProbe probe;
     auto chunk = [&](uint32_t base) __attribute__((always_inline)) {
         probe.start();
-        topup_st<KIND, LAY, WALK, WBR>(rd, pd, sg, dummy);
+        // (a staged chunk is always the chunk before: sg.mask is 0 at the first)
+        topup_st<KIND, LAY, WALK, WBR>(rd, pd, sg, dummy, base - (uint32_t)L_);
         sg.mask = 0;  // flushed
         probe.after_topup();
-        if (L.mode == M_PRED && base < L.bs && base >= (uint32_t)L.order && L.left == 0 && L.parts_left > 0)
-            read_partition_header<KIND>(L, rd);
+        const bool part_hdr =
+            L.mode == M_PRED && base < L.bs && base >= (uint32_t)L.order && L.left == 0 && L.parts_left > 0;
+        if constexpr (HOLD) sel_stale += count(part_hdr);  // (at most 64 a chunk, and reset below: no wrap)
+        if (part_hdr) read_partition_header<KIND>(L, rd);
         if (L.mode != M_NONE && rd.pos() > L.end) set_err(L, rd, E_END_OF_STREAM);
         const bool active = L.mode != M_NONE && base < L.bs;
         // The first chunk is fast too: its warm-up samples are re-emitted from the history.
@@ -162,10 +190,20 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
             constexpr auto has = [](auto form) { return decltype(form)::template in_kernel<KIND, LAY, MIX, WALK>(); };
             constexpr bool PAIRS = has(FormPair{});
             // (decode: k >= 2, for rice_step's residual form; the walk takes k = 1 too)
-            const bool pairs = PAIRS && pair_cool == 0 && base != 0 &&
-                               __builtin_amdgcn_ballot_w64(lane_fast && (L.k < (WALK ? 1u : 2u) || L.k > PAIR_KMAX ||
-                                                                         L.esc)) == 0;
-            const bool escs = __builtin_amdgcn_ballot_w64(lane_fast && L.esc) != 0;
+            bool pairs, escs;
+            if constexpr (HOLD) {
+                if (sel_stale) {  // (see above)
+                    sel_stale = 0;
+                    k_bad = count(lane_fast && (L.k < (WALK ? 1u : 2u) || L.k > PAIR_KMAX || L.esc));
+                    esc_n = count(lane_fast && L.esc);
+                }
+                pairs = PAIRS && pair_cool == 0 && base != 0 && k_bad == 0;
+                escs = esc_n != 0;
+            } else {
+                pairs = PAIRS && pair_cool == 0 && base != 0 &&
+                        __builtin_amdgcn_ballot_w64(lane_fast && (L.k < (WALK ? 1u : 2u) || L.k > PAIR_KMAX || L.esc)) == 0;
+                escs = __builtin_amdgcn_ballot_w64(lane_fast && L.esc) != 0;
+            }
             // 31/32-bit stereo with decorrelation: the per-sample overflow-checking variant (the
             // generic one-code form, escapes and warm-up included, with the checks), see fast_chunk
             bool wide = false;
@@ -178,6 +216,7 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
             // ladder's arms below the escapes, like the k >= 2 test of the mono one-code chunks
             // (C2 after its pair back-off).
             auto all_ms = [&]() {
+                if constexpr (HOLD) return ms_bad == 0;
                 bool ms = true;
                 if constexpr (LAY == LAY_STEREO) ms = __builtin_amdgcn_ballot_w64(lane_fast && L.chan_code != 10) == 0;
                 if constexpr (KIND == 1)
@@ -255,14 +294,17 @@ __device__ __forceinline__ void run_subframe(LaneCtx& L, Rdr& rd, const FrameCtx
             }
         }
         probe.after_fast(need_slow);
-        if (redo) slow_chunk<KIND, M, L_, LAY, WALK>(L, rd, pr, base, fc, out, nch, c, c1m);
+        if (redo) {
+            slow_chunk<KIND, M, L_, LAY, WALK>(L, rd, pr, base, fc, out, nch, c, c1m);
+            if constexpr (HOLD) sel_stale = 1;
+        }
         probe.after_slow(redo);
     };
     for (uint32_t base = 0; base < bs_max; base += L_) chunk(base);
     probe.finish(dummy_base, WALK);
     if constexpr (!WALK) {
         if constexpr (staged<KIND, LAY>()) {
-            sg.template flush<WBR>(dummy);
+            sg.template flush<WBR>(dummy, __builtin_amdgcn_readfirstlane(sg.base));
         } else {
             pd.flush(pend_two<KIND>());
         }
