@@ -1,9 +1,6 @@
 // abi.cpp -- the extern "C" ABI of include/zflac_hip.h over the host units (batch.h), the
 // batch's destructor, the build id, and the entry points of the diagnostic builds.
-#include <cmath>
 #include <cstring>
-#include <new>
-#include <vector>
 
 #include "batch.h"
 #include "launch.h"
@@ -42,168 +39,6 @@ zflac_batch::~zflac_batch() {
     if (front) (void)hipStreamDestroy(front);
     if (front_join) (void)hipEventDestroy(front_join);
 }
-
-// ---- dense export: what zflac_hip_batch_export and zflac_hip_batch_export_resampled share ----
-namespace {
-
-struct ExportShape {
-    size_t n;
-    uint64_t T, C, esz, tiles;
-    uint32_t vec;
-};
-
-// the checks both exports make, in the plain export's order (max_dtype: the last dtype the call takes)
-bool export_shape(zflac_batch* b, uint32_t size, uint32_t want_size, int dtype, int max_dtype, int layout,
-                  uint64_t channels, uint64_t frames, const void* dst, size_t dst_bytes, ExportShape& s) {
-    if (!b || !dst || size != want_size) return false;
-    if (dtype > max_dtype || layout > ZFLAC_LAYOUT_INTERLEAVED || !channels || !frames) return false;
-    if (!b->ran || b->submitted) return false;
-    s.n = b->streams.size();
-    s.T = frames;
-    s.C = channels;
-    s.esz = (dtype == ZFLAC_EXPORT_F16 || dtype == ZFLAC_EXPORT_BF16) ? 2 : 4;
-    const unsigned __int128 need = (unsigned __int128)s.n * s.C * s.T * s.esz;  // < 2^64 * 2^16 * 2^64 * 4
-    if (need > (unsigned __int128)dst_bytes) return false;
-    s.tiles = (s.T + EXPORT_TILE - 1) / EXPORT_TILE;
-    if ((unsigned __int128)s.n * s.tiles > 0x7FFFFFFFull) return false;  // gridDim.x
-    const uint64_t row_bytes = (layout == ZFLAC_LAYOUT_PLANAR ? s.T : s.T * s.C) * s.esz;
-    s.vec = (reinterpret_cast<uintptr_t>(dst) % 16 == 0 && row_bytes % 16 == 0) ? 1u : 0u;
-    return true;
-}
-
-// stream i as k_export's row record; r.src stays null unless the stream has frames from `start` on
-ExportRow export_row(const StreamState& s, uint64_t start) {
-    ExportRow r;
-    std::memset(&r, 0, sizeof(r));
-    r.start = start;
-    r.kind = s.info.sample_kind;
-    if (!s.err && s.info.channels && s.dev_samples) {
-        r.nch = s.info.channels;
-        r.n_frames = s.info.n_samples / s.info.channels;
-        if (r.start < r.n_frames) r.src = s.dev_samples;
-    }
-    return r;
-}
-
-// The matrices of a mixed export, checked and laid out as the kernels read them: at[n] is where
-// the C x n matrix of the n-channel streams starts in `table` (0: none, the fit rule), table[0] is
-// unused. any: the call has a matrix and launches the mixed kernel.
-struct MixPlan {
-    bool any = false;
-    uint16_t at[MIX_MAX_CH + 1] = {};
-    std::vector<float> table;
-};
-
-// zflac_mix_desc's rules (mix may be NULL). Every non-NULL matrix is read here, so the caller may
-// free it when the call returns.
-bool mix_plan(const zflac_mix_desc* mix, int dtype, uint64_t channels, MixPlan& p) {
-    if (!mix) return true;
-    if (mix->size != sizeof(zflac_mix_desc) || mix->reserved) return false;
-    static_assert(ZFLAC_MIX_MAX_CHANNELS == MIX_MAX_CH, "zflac_hip.h and common.h disagree");
-    for (uint32_t n = 1; n <= MIX_MAX_CH; n++) {
-        const float* m = mix->matrix[n - 1];
-        if (!m) continue;
-        if (dtype == ZFLAC_EXPORT_I32 || channels > MIX_MAX_CH) return false;
-        if (!p.any) p.table.assign(1, 0.0f);
-        p.any = true;
-        p.at[n] = (uint16_t)p.table.size();
-        for (uint64_t i = 0; i < channels * n; i++) {
-            const float a = std::fabs(m[i]);  // (NaN fails the range test)
-            if (a != 0.0f && !(a >= 0x1p-64f && a <= 0x1p64f)) return false;
-            p.table.push_back(a == 0.0f ? 0.0f : m[i]);
-        }
-    }
-    return true;
-}
-
-// ExportRow::mix of a stream of nch channels
-uint16_t mix_at(const MixPlan& p, uint32_t nch) { return nch <= MIX_MAX_CH ? p.at[nch] : 0; }
-
-// bytes of n row records with the coefficient table behind them (16-byte aligned)
-size_t mix_table_offset(size_t row_bytes) { return (row_bytes + 15) & ~(size_t)15; }
-
-// Before the row records are written: the buffers exist and the last export has let go of them.
-// Returns whether this export is timed.
-bool export_begin(zflac_batch* b, size_t n, void* stream, hipStream_t st) {
-    if (!b->exp_pin) {
-        // room for the larger record and for a mixed export's coefficient table behind the records
-        const size_t bytes = mix_table_offset(n * sizeof(ResampleRow)) + MIX_TABLE_FLOATS * sizeof(float);
-        ck(hipHostMalloc(reinterpret_cast<void**>(&b->exp_pin), bytes, hipHostMallocDefault));
-        b->exp_rows.alloc(bytes);
-        ck(hipEventCreateWithFlags(&b->ev_exp_copy, hipEventDisableTiming));
-        ck(hipEventCreateWithFlags(&b->ev_exp, hipEventDisableTiming));
-    }
-    if (b->exp_any) {
-        ck(hipEventSynchronize(b->ev_exp_copy));     // the last export's copy has read exp_pin
-        ck(hipStreamWaitEvent(st, b->ev_exp, 0));    // and its kernel exp_rows, before this copy lands
-    }
-    const bool timed = !stream && (b->flags & ZFLAC_FLAG_TIMING);
-    if (timed)
-        for (auto& e : b->ev_exp_t)
-            if (!e) ck(hipEventCreate(&e));
-    return timed;
-}
-
-// After the row records (row_bytes of them) are in exp_pin: the coefficient table goes behind
-// them, so that one copy takes both. Returns the table's device address (null without a matrix)
-// and grows `bytes`, what export_run copies.
-const float* mix_stage(zflac_batch* b, const MixPlan& p, size_t row_bytes, size_t& bytes) {
-    bytes = row_bytes;
-    if (!p.any) return nullptr;
-    const size_t at = mix_table_offset(row_bytes);
-    std::memset(b->exp_pin + row_bytes, 0, at - row_bytes);
-    std::memcpy(b->exp_pin + at, p.table.data(), p.table.size() * sizeof(float));
-    bytes = at + p.table.size() * sizeof(float);
-    return reinterpret_cast<const float*>(b->exp_rows.p + at);
-}
-
-// The records are in exp_pin: copy them, launch, and finish as the caller's stream asks.
-template <typename Launch>
-void export_run(zflac_batch* b, size_t bytes, bool timed, void* stream, hipStream_t st, Launch launch) {
-    if (timed) ck(hipEventRecord(b->ev_exp_t[0], st));
-    ck(hipMemcpyAsync(b->exp_rows.p, b->exp_pin, bytes, hipMemcpyHostToDevice, st));
-    ck(hipEventRecord(b->ev_exp_copy, st));
-    const hipError_t le = launch();
-    ck(hipEventRecord(b->ev_exp, st));  // (also after a failed launch: the copy above is enqueued)
-    b->exp_any = true;
-    ck(le);
-    if (timed) ck(hipEventRecord(b->ev_exp_t[1], st));
-    if (stream) {
-        b->exp_pending = true;
-    } else {
-        ck(hipStreamSynchronize(st));
-        if (timed) {
-            float ms = 0;
-            ck(hipEventElapsedTime(&ms, b->ev_exp_t[0], b->ev_exp_t[1]));
-            b->export_ms = ms;
-        }
-    }
-}
-
-// The batch's table for these parameters: the one it holds, or a new one (built on the host,
-// uploaded before this returns).
-ResampleTable* resample_table(zflac_batch* b, uint32_t fin, const zflac_resample_desc* d, const ResampleRatio& ratio) {
-    for (auto& t : b->rs_tables)
-        if (t->fin == fin && t->fout == d->sample_rate && t->zeros == d->zeros && t->rolloff == d->rolloff &&
-            t->beta == d->beta)
-            return t.get();
-    auto t = std::make_unique<ResampleTable>();
-    t->fin = fin;
-    t->fout = d->sample_rate;
-    t->zeros = d->zeros;
-    t->rolloff = d->rolloff;
-    t->beta = d->beta;
-    t->ratio = ratio;
-    std::vector<float> h;
-    resample_taps(ratio, d->zeros, d->beta, h);
-    t->taps.alloc(h.size());
-    ck(hipMemcpy(t->taps.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    b->rs_built++;
-    b->rs_tables.push_back(std::move(t));
-    return b->rs_tables.back().get();
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -265,38 +100,25 @@ static void drain_failed_submit(zflac_batch* b) {
 int zflac_hip_batch_submit(zflac_batch* b) {
     if (!b || b->submitted) return E_INVALID_ARGUMENT;
     b->ran = false;
-    try {
+    const int rc = guarded([&]() -> int {
         b->submit_t0 = now_ms();
         b->submitted = true;
         submit_batch(b);
-    } catch (const DeviceError&) {
-        drain_failed_submit(b);
-        return E_DEVICE;
-    } catch (const std::bad_alloc&) {
-        drain_failed_submit(b);
-        return E_OUT_OF_MEMORY;
-    } catch (const std::exception&) {
-        drain_failed_submit(b);
-        return E_DEVICE;
-    }
-    return E_OK;
+        return E_OK;
+    });
+    if (rc) drain_failed_submit(b);
+    return rc;
 }
 
 int zflac_hip_batch_wait(zflac_batch* b) {
     if (!b || !b->submitted) return E_INVALID_ARGUMENT;
     b->submitted = false;
-    int rc = E_OK;
-    try {
+    const int rc = guarded([&]() -> int {
         finish_batch(b);
         b->timings.run_wall_ms = now_ms() - b->submit_t0;
         b->ran = true;
-    } catch (const DeviceError&) {
-        rc = E_DEVICE;
-    } catch (const std::bad_alloc&) {
-        rc = E_OUT_OF_MEMORY;
-    } catch (const std::exception&) {
-        rc = E_DEVICE;
-    }
+        return E_OK;
+    });
     if (rc != E_OK && b->md5_pending) {  // failed before the hub released this run
         try {
             hub_forget(b);
@@ -354,15 +176,11 @@ int zflac_hip_batch_read(zflac_batch* b, size_t i, void* out, size_t out_bytes, 
     StreamState& s = b->streams[i];
     if (s.err) return s.err;
     if (out_bytes < s.info.samples_bytes || (!out && s.info.samples_bytes)) return E_INVALID_ARGUMENT;
-    try {
+    return guarded([&]() -> int {
         ck(hipSetDevice(b->device));
         // a device verdict stands in for the host hash (a mismatch is already s.err)
         return read_samples(b, s, out, verify_md5 && !s.md5_dev);  // InvalidChecksum at :279-280
-    } catch (const DeviceError&) {
-        return E_DEVICE;
-    } catch (const std::exception&) {  // std::system_error: the hashing thread could not start
-        return E_DEVICE;
-    }
+    });
 }
 
 int zflac_hip_batch_md5(zflac_batch* b, size_t i, uint8_t* digest) {
@@ -388,219 +206,28 @@ int zflac_hip_batch_timings_ex(zflac_batch* b, zflac_timings* t, size_t size) {
 
 int zflac_hip_abi_version(void) { return ZFLAC_HIP_ABI_VERSION; }
 
-// zflac_hip_batch_export (mix == NULL) and zflac_hip_batch_export_mixed
-static int export_plain(zflac_batch* b, const zflac_export_desc* d, const zflac_mix_desc* mix, void* dst_device,
-                        size_t dst_bytes, uint64_t* valid_frames, void* stream) {
-    ExportShape s;
-    MixPlan mp;
-    if (!d || !export_shape(b, d->size, sizeof(zflac_export_desc), d->dtype, ZFLAC_EXPORT_I32, d->layout, d->channels,
-                            d->frames, dst_device, dst_bytes, s))
-        return E_INVALID_ARGUMENT;
-    try {
-        if (!mix_plan(mix, d->dtype, s.C, mp)) return E_INVALID_ARGUMENT;
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    }
-    const size_t n = s.n;
-    for (size_t i = 0; valid_frames && i < n; i++) {
-        const StreamState& st = b->streams[i];
-        const uint64_t start = d->starts ? d->starts[i] : 0;
-        const uint64_t nf = (st.err || !st.info.channels) ? 0 : st.info.n_samples / st.info.channels;
-        valid_frames[i] = nf > start ? std::min(nf - start, s.T) : 0;
-    }
-    if (n == 0) return E_OK;
-    try {
-        DeviceScope scope(b->device);
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->stream;
-        const bool timed = export_begin(b, n, stream, st);
-        ExportRow* rows = reinterpret_cast<ExportRow*>(b->exp_pin);
-        for (size_t i = 0; i < n; i++) {
-            rows[i] = export_row(b->streams[i], d->starts ? d->starts[i] : 0);
-            rows[i].mix = mix_at(mp, rows[i].nch);
-        }
-        size_t bytes;
-        const float* coef = mix_stage(b, mp, n * sizeof(ExportRow), bytes);
-        ExportArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.rows = reinterpret_cast<const ExportRow*>(b->exp_rows.p);
-        a.dst = dst_device;
-        a.frames = s.T;
-        a.channels = (uint32_t)s.C;
-        a.n_rows = (uint32_t)n;
-        a.tiles = (uint32_t)s.tiles;
-        a.vec = s.vec;
-        export_run(b, bytes, timed, stream, st, [&] {  // without a matrix: k_export, as ever
-            return coef ? launch_export_mixed(d->dtype, d->layout, a, coef, st) : launch_export(d->dtype, d->layout, a, st);
-        });
-    } catch (const DeviceError&) {
-        return E_DEVICE;
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    }
-    return E_OK;
-}
-
 int zflac_hip_batch_export(zflac_batch* b, const zflac_export_desc* d, void* dst_device, size_t dst_bytes,
                            uint64_t* valid_frames, void* stream) {
-    return export_plain(b, d, nullptr, dst_device, dst_bytes, valid_frames, stream);
+    return export_dense(b, export_call(d), nullptr, dst_device, dst_bytes, valid_frames, stream);
 }
 
 int zflac_hip_batch_export_mixed(zflac_batch* b, const zflac_export_desc* d, const zflac_mix_desc* mix,
                                  void* dst_device, size_t dst_bytes, uint64_t* valid_frames, void* stream) {
-    return export_plain(b, d, mix, dst_device, dst_bytes, valid_frames, stream);
+    return export_dense(b, export_call(d), mix, dst_device, dst_bytes, valid_frames, stream);
 }
 
 uint64_t zflac_hip_resampled_frames(uint64_t n_frames, uint32_t rate_in, uint32_t rate_out) {
     return resampled_frames(n_frames, rate_in, rate_out);
 }
 
-// zflac_hip_batch_export_resampled (mix == NULL) and zflac_hip_batch_export_resampled_mixed
-static int export_resampled(zflac_batch* b, const zflac_resample_desc* d, const zflac_mix_desc* mix, void* dst_device,
-                            size_t dst_bytes, uint64_t* valid_frames, void* stream) {
-    ExportShape s;
-    MixPlan mp;
-    if (!d || !export_shape(b, d->size, sizeof(zflac_resample_desc), d->dtype, ZFLAC_EXPORT_BF16, d->layout,
-                            d->channels, d->frames, dst_device, dst_bytes, s))
-        return E_INVALID_ARGUMENT;
-    if (!d->sample_rate || d->sample_rate > RESAMPLE_MAX_RATE || d->reserved ||
-        !resample_params_ok(d->zeros, d->rolloff, d->beta))
-        return E_INVALID_ARGUMENT;
-    try {
-        if (!mix_plan(mix, d->dtype, s.C, mp)) return E_INVALID_ARGUMENT;
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    }
-    // channels of stream `st` that k_resample stages: min(its own, C), or C when it is mixed first
-    auto staged = [&](const StreamState& st) {
-        return mix_at(mp, st.info.channels) ? s.C : std::min<uint64_t>(st.info.channels, s.C);
-    };
-    const size_t n = s.n;
-    // What each row takes, before anything is written or enqueued. plan[i] < 0: k_export's
-    // paths (same rate, error, rate 0); else the index of the row's ratio in `ratios`.
-    struct Need {
-        uint32_t fin;
-        ResampleRatio ratio;
-    };
-    std::vector<Need> needs;
-    std::vector<int> plan(n, -1);
-    std::vector<uint64_t> n_out(n, 0);
-    uint64_t floats = 0, tiles = s.tiles;
-    try {
-        for (size_t i = 0; i < n; i++) {
-            const StreamState& st = b->streams[i];
-            if (st.err || !st.info.channels || !st.info.sample_rate) continue;
-            const uint64_t nf = st.info.n_samples / st.info.channels;
-            const uint32_t fin = st.info.sample_rate;
-            if (fin == d->sample_rate) {
-                n_out[i] = nf;
-                continue;
-            }
-            n_out[i] = resampled_frames(nf, fin, d->sample_rate);
-            int k = 0;
-            while (k < (int)needs.size() && needs[k].fin != fin) k++;
-            if (k == (int)needs.size()) {
-                Need nd;
-                nd.fin = fin;
-                if (!resample_ratio(fin, d->sample_rate, d->zeros, d->rolloff, nd.ratio)) return E_INVALID_ARGUMENT;
-                if (nd.ratio.K > RESAMPLE_MAX_TAPS) return E_INVALID_ARGUMENT;
-                floats += nd.ratio.table_floats();
-                if (floats > RESAMPLE_MAX_TABLE_FLOATS) return E_INVALID_ARGUMENT;
-                needs.push_back(nd);
-            }
-            plan[i] = k;
-            const ResampleTile rt = resample_tile(needs[k].ratio, (uint32_t)staged(st));
-            tiles = std::max(tiles, (s.T + rt.tile - 1) / rt.tile);
-        }
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    }
-    if ((unsigned __int128)n * tiles > 0x7FFFFFFFull) return E_INVALID_ARGUMENT;  // gridDim.x
-    for (size_t i = 0; valid_frames && i < n; i++) {
-        const uint64_t start = d->starts ? d->starts[i] : 0;
-        valid_frames[i] = n_out[i] > start ? std::min(n_out[i] - start, s.T) : 0;
-    }
-    if (n == 0) return E_OK;
-    try {
-        DeviceScope scope(b->device);
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : b->stream;
-        // Tables this call needs and the batch does not hold. Were they to take the batch past the
-        // limit, the tables this call does not need go first (hipFree waits for the device, so
-        // for any earlier export that reads them).
-        uint64_t held = 0;
-        for (auto& t : b->rs_tables) held += t->ratio.table_floats();
-        if (held + floats > RESAMPLE_MAX_TABLE_FLOATS) {
-            std::erase_if(b->rs_tables, [&](const std::unique_ptr<ResampleTable>& t) {
-                if (t->fout == d->sample_rate && t->zeros == d->zeros && t->rolloff == d->rolloff && t->beta == d->beta)
-                    for (const Need& nd : needs)
-                        if (nd.fin == t->fin) return false;
-                return true;
-            });
-        }
-        std::vector<const ResampleTable*> tabs;
-        for (const Need& nd : needs) tabs.push_back(resample_table(b, nd.fin, d, nd.ratio));
-        const bool timed = export_begin(b, n, stream, st);
-        ResampleRow* rows = reinterpret_cast<ResampleRow*>(b->exp_pin);
-        for (size_t i = 0; i < n; i++) {
-            const StreamState& ss = b->streams[i];
-            ResampleRow r;
-            std::memset(&r, 0, sizeof(r));
-            const uint64_t start = d->starts ? d->starts[i] : 0;
-            if (plan[i] < 0) {
-                r.e = export_row(ss, start);
-                if (!n_out[i]) r.e.src = nullptr;  // a stream whose rate is 0: a zero row
-            } else {
-                const ResampleTable* t = tabs[plan[i]];
-                const ResampleTile rt = resample_tile(t->ratio, (uint32_t)staged(ss));
-                r.e = export_row(ss, 0);  // (src by the source's length ...)
-                r.e.start = start;        // ... the window by the resampled stream's)
-                r.n_out = n_out[i];
-                if (r.e.src && start < r.n_out) {
-                    r.taps = t->taps.p;
-                    r.L = t->ratio.L;
-                    r.M = t->ratio.M;
-                    r.W = t->ratio.W;
-                    r.K = (uint32_t)t->ratio.K;
-                    r.tile = rt.tile;
-                    r.cg = rt.cg;
-                    r.tab_lds = rt.tab_lds;
-                } else {
-                    r.e.src = nullptr;  // no frames, or the window is past the end: a zero row
-                }
-            }
-            r.e.mix = mix_at(mp, r.e.nch);
-            rows[i] = r;
-        }
-        size_t bytes;
-        const float* coef = mix_stage(b, mp, n * sizeof(ResampleRow), bytes);
-        ResampleArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.rows = reinterpret_cast<const ResampleRow*>(b->exp_rows.p);
-        a.dst = dst_device;
-        a.frames = s.T;
-        a.channels = (uint32_t)s.C;
-        a.n_rows = (uint32_t)n;
-        a.tiles = (uint32_t)tiles;
-        a.vec = s.vec;
-        export_run(b, bytes, timed, stream, st, [&] {  // without a matrix: k_resample, as ever
-            return coef ? launch_resample_mixed(d->dtype, d->layout, a, coef, st)
-                        : launch_resample(d->dtype, d->layout, a, st);
-        });
-    } catch (const DeviceError&) {
-        return E_DEVICE;
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    }
-    return E_OK;
-}
-
 int zflac_hip_batch_export_resampled(zflac_batch* b, const zflac_resample_desc* d, void* dst_device, size_t dst_bytes,
                                      uint64_t* valid_frames, void* stream) {
-    return export_resampled(b, d, nullptr, dst_device, dst_bytes, valid_frames, stream);
+    return export_dense(b, export_call(d), nullptr, dst_device, dst_bytes, valid_frames, stream);
 }
 
 int zflac_hip_batch_export_resampled_mixed(zflac_batch* b, const zflac_resample_desc* d, const zflac_mix_desc* mix,
                                            void* dst_device, size_t dst_bytes, uint64_t* valid_frames, void* stream) {
-    return export_resampled(b, d, mix, dst_device, dst_bytes, valid_frames, stream);
+    return export_dense(b, export_call(d), mix, dst_device, dst_bytes, valid_frames, stream);
 }
 
 int zflac_hip_batch_resample_tables(zflac_batch* b, uint64_t* built, uint64_t* held_floats) {

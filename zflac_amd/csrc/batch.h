@@ -1,5 +1,5 @@
 // batch.h -- the types the host units share (pipeline.cpp, seq_planner.cpp, md5_host.cpp,
-// abi.cpp): device buffers, a stream's and a class's state, the per-device run streams and
+// export_host.cpp, abi.cpp): device buffers, a stream's and a class's state, the per-device run streams and
 // md5 hub, the batch itself, and the prototypes of the functions one unit calls in another.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,10 +10,12 @@
 #include <cstdint>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "export_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
 
@@ -26,6 +28,20 @@ inline double now_ms() {
 struct DeviceError {};
 inline void ck(hipError_t e) {
     if (e != hipSuccess) throw DeviceError{};
+}
+
+// The C boundary: the code `f` returns, or the one that stands for what it threw. Nothing leaves.
+template <typename F>
+int guarded(F&& f) noexcept {
+    try {
+        return f();
+    } catch (const DeviceError&) {
+        return E_DEVICE;
+    } catch (const std::bad_alloc&) {
+        return E_OUT_OF_MEMORY;
+    } catch (...) {  // e.g. std::system_error: a helper thread could not start
+        return E_DEVICE;
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -227,6 +243,12 @@ int create_batch(const zflac_stream* streams, size_t n, int device, int flags, z
 void finish_stream_sequential(zflac_batch* b, Class& C, uint32_t slot, const std::vector<uint32_t>& h_chunk_off,
                               uint32_t nframes);
 
+// export_host.cpp
+// The four dense exports: plan (export_plan.h), write the row records, stage the tables, launch,
+// and finish as the caller's stream asks.
+int export_dense(zflac_batch* b, const ExportCall& call, const zflac_mix_desc* mix, void* dst, size_t dst_bytes,
+                 uint64_t* valid_frames, void* stream);
+
 }  // namespace zflac
 
 // ---------------------------------------------------------------------------------
@@ -281,6 +303,9 @@ struct zflac_batch {
     // run's streams before they overwrite the samples, and the destructor on the host).
     uint8_t* exp_pin = nullptr;
     zflac::DevBuf<uint8_t> exp_rows;
+    // the streams as the export planner sees them: scratch of one call (refilled by each, nothing
+    // carried between calls), kept here only so that a call allocates nothing
+    std::vector<zflac::ExportStream> exp_views;
     hipEvent_t ev_exp_copy = nullptr, ev_exp = nullptr;
     hipEvent_t ev_exp_t[2] = {};  // ZFLAC_FLAG_TIMING: around a synchronous export
     bool exp_any = false;      // ev_exp_copy / ev_exp have been recorded

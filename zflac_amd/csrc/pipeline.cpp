@@ -749,7 +749,7 @@ int create_batch(const zflac_stream* streams, size_t n, int device, int flags, z
     if (!b) return E_OUT_OF_MEMORY;
     b->device = device;
     b->flags = flags;
-    try {
+    const int rc = guarded([&]() -> int {
         ck(hipSetDevice(device));
         (void)device_streams(device);  // the run and md5 hub streams first (their own hardware queues)
         ck(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
@@ -800,13 +800,9 @@ int create_batch(const zflac_stream* streams, size_t n, int device, int flags, z
                 s.info.sample_kind = (uint8_t)s.kind;
             }
         }
-    } catch (const DeviceError&) {
-        return E_DEVICE;
-    } catch (const std::bad_alloc&) {
-        return E_OUT_OF_MEMORY;
-    } catch (const std::exception&) {  // e.g. std::system_error from an upload helper thread
-        return E_DEVICE;
-    }
+        return E_OK;
+    });
+    if (rc) return rc;
     *out = b.release();
     return E_OK;
 }
