@@ -349,6 +349,75 @@ int zflac_hip_batch_export_mixed(zflac_batch *b, const zflac_export_desc *d, con
 int zflac_hip_batch_export_resampled_mixed(zflac_batch *b, const zflac_resample_desc *d, const zflac_mix_desc *mix,
                                            void *dst_device, size_t dst_bytes, uint64_t *valid_frames, void *stream);
 
+/* ---- log-mel features of a dense f32 waveform ---------------------------------------- */
+/* From the planar f32 tensor the exports write (or any dense f32 rows in device memory) to
+ * [row][bin][frame] features in one launch of one HIP kernel (k_mel): a windowed DFT as an f32
+ * matrix product on the matrix cores, the power spectrum, a filterbank as a second f32 matrix
+ * product, an optional log. A plan (zflac_mel) holds the tables; a run turns a waveform into
+ * features.
+ *
+ * Row i of the waveform is x_i[s] = wave_device[i * row_stride + s] for 0 <= s < wave_frames and
+ * zero outside that range (a [B, C, T] planar export is B * C rows of stride T). With N = n_fft,
+ * K = N / 2 + 1 and off = center ? N / 2 : 0, feature frame t = first_frame + j (j < frames) is
+ *   re[k] = sum_n c[n][k] * x_i[t * hop - off + n]     im[k] = sum_n s[n][k] * x_i[...]   k < K
+ *   c[n][k] = (float)( window[n] * cos(2 pi ((n k) mod N) / N) )
+ *   s[n][k] = (float)(-window[n] * sin(2 pi ((n k) mod N) / N) )
+ *   P[k] = re[k]^2 + im[k]^2
+ *   v[m] = sum_k filters[m][k] * P[k]                  m < n_bins
+ * The tables are built in double from the caller's floats and rounded once; s[.][0] and
+ * s[.][N / 2] are exactly 0. out[i][m][j] is v[m] (ZFLAC_MEL_POWER), log10f(max(v[m], floor)) or
+ * logf(max(v[m], floor)), then rounded to f16 or bf16 exactly as the plain export rounds its f32
+ * value. All sums are f32; the order of summation is the kernel's, the same for every frame: the
+ * bits of a frame do not depend on rows, frames, first_frame, where the frame falls in a tile or
+ * the alignment of wave_device. A frame with no non-zero sample under it has P = +0 everywhere,
+ * so v = +0 and a log output of exactly log(floor). Every element of the destination is written.
+ *
+ * Padding is zeros only. There is no reflect mode: with center = 1 the first and the last
+ * N / (2 hop) frames differ from those of a reflect-padded STFT (torch.stft's default). */
+#define ZFLAC_MEL_POWER 0   /* the filterbank sums as they are */
+#define ZFLAC_MEL_LOG10 1   /* log10f(max(v, floor)) */
+#define ZFLAC_MEL_LN    2   /* logf(max(v, floor)) */
+#define ZFLAC_MEL_BINS_FIRST   0  /* [row][bin][frame] */
+#define ZFLAC_MEL_FRAMES_FIRST 1  /* [row][frame][bin] */
+typedef struct zflac_mel_desc {
+    uint32_t size;                        /* sizeof(zflac_mel_desc): 40 on LP64 */
+    uint8_t dtype, layout, scale, center; /* ZFLAC_EXPORT_F32/_F16/_BF16; ZFLAC_MEL_*; center 0 or 1 */
+    uint16_t n_fft;                       /* N: even, 2..2048 */
+    uint16_t hop;                         /* 1..N */
+    uint16_t n_bins;                      /* rows of `filters`: 1..256 */
+    uint16_t reserved;                    /* must be 0 */
+    float floor;                          /* log scales: finite and > 0; ZFLAC_MEL_POWER: must be 0 */
+    const float *window;                  /* host, N floats */
+    const float *filters;                 /* host, n_bins x (N/2 + 1) floats, row-major */
+} zflac_mel_desc;
+typedef struct zflac_mel zflac_mel;
+/* A plan on `device`. The arguments are checked first and the device is touched afterwards (on a
+ * machine without a GPU a good descriptor returns ZFLAC_E_DEVICE, a bad one
+ * ZFLAC_E_INVALID_ARGUMENT); the host arrays are read before the call returns.
+ * ZFLAC_E_INVALID_ARGUMENT: NULL d, out, window or filters; a wrong size; an unknown dtype
+ * (ZFLAC_EXPORT_I32 included), layout or scale; center > 1; n_fft odd or outside 2..2048; hop of 0
+ * or above n_fft; n_bins outside 1..256; reserved != 0; a floor outside its rule; a non-finite
+ * window or filter value. */
+int zflac_hip_mel_create(const zflac_mel_desc *d, int device, zflac_mel **out);
+/* dst_device: rows * n_bins * frames elements of the plan's dtype, [row][bin][frame] or
+ * [row][frame][bin]. Frames at or past zflac_hip_mel_frames() are still computed, from the
+ * zero-extended row. stream == NULL: runs on the plan's own stream and returns when the tensor is
+ * complete; otherwise the launch is enqueued on that hipStream_t of the plan's device without
+ * synchronising. A run stages nothing (the tables are immutable, the arguments go by value), so
+ * runs of one plan on different streams may overlap. rows == 0: ZFLAC_OK, nothing done.
+ * ZFLAC_E_INVALID_ARGUMENT (nothing enqueued): NULL m, wave_device or dst_device; a wave_device
+ * that is not 4-byte aligned; row_stride < wave_frames; frames == 0; dst_bytes < rows * n_bins *
+ * frames * element size; (first_frame + frames) * hop not fitting 63 bits (nor rows * row_stride
+ * 61); more than 2^31 - 1 workgroups (rows * ceil(frames / 128)). */
+int zflac_hip_mel_run(zflac_mel *m, const float *wave_device, uint64_t rows, uint64_t wave_frames,
+                      uint64_t row_stride, uint64_t first_frame, uint64_t frames,
+                      void *dst_device, size_t dst_bytes, void *stream);
+/* Frames of a centred (n ? n / hop + 1 : 0) or uncentred (n >= n_fft ? (n - n_fft) / hop + 1 : 0)
+ * STFT of n_samples: what callers use as the valid length. 0 when hop is 0. Host arithmetic. */
+uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center);
+/* Waits for the device, then frees the plan. NULL is ignored. */
+void zflac_hip_mel_destroy(zflac_mel *m);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -404,7 +473,9 @@ const char *zflac_hip_build_id(void);
  *    zflac_resample_desc, zflac_hip_batch_export_resampled, zflac_hip_resampled_frames,
  *    zflac_hip_batch_resample_tables; zflac_hip_batch_decode_buckets, ZFLAC_BUCKET_*;
  *    zflac_hip_batch_front, ZFLAC_FRONT_*, ZFLAC_FLAG_FRONT_*; zflac_mix_desc,
- *    ZFLAC_MIX_MAX_CHANNELS, zflac_hip_batch_export_mixed, zflac_hip_batch_export_resampled_mixed. */
+ *    ZFLAC_MIX_MAX_CHANNELS, zflac_hip_batch_export_mixed, zflac_hip_batch_export_resampled_mixed;
+ *    zflac_mel_desc, zflac_mel, ZFLAC_MEL_*, zflac_hip_mel_create, zflac_hip_mel_run,
+ *    zflac_hip_mel_frames, zflac_hip_mel_destroy. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

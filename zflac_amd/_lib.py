@@ -50,6 +50,14 @@ class zflac_mix_desc(ctypes.Structure):
                 ("matrix", ctypes.POINTER(ctypes.c_float) * 8)]
 
 
+class zflac_mel_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_uint8), ("layout", ctypes.c_uint8),
+                ("scale", ctypes.c_uint8), ("center", ctypes.c_uint8), ("n_fft", ctypes.c_uint16),
+                ("hop", ctypes.c_uint16), ("n_bins", ctypes.c_uint16), ("reserved", ctypes.c_uint16),
+                ("floor", ctypes.c_float), ("window", ctypes.POINTER(ctypes.c_float)),
+                ("filters", ctypes.POINTER(ctypes.c_float))]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -86,6 +94,11 @@ SIGNATURES = {
     "zflac_hip_resampled_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
     "zflac_hip_batch_resample_tables": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64),
                                                        ctypes.POINTER(ctypes.c_uint64)]),
+    "zflac_hip_mel_create": (ctypes.c_int, [ctypes.POINTER(zflac_mel_desc), ctypes.c_int, ctypes.POINTER(_P)]),
+    "zflac_hip_mel_run": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_uint64, _P, ctypes.c_size_t, _P]),
+    "zflac_hip_mel_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
+    "zflac_hip_mel_destroy": (None, [_P]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -113,6 +126,12 @@ EXPORT_I32 = 3
 LAYOUT_PLANAR = 0
 LAYOUT_INTERLEAVED = 1
 MIX_MAX_CHANNELS = 8  # zflac_mix_desc: C and n of a matrix, at most
+# zflac_mel_desc: scale and layout of the features
+MEL_POWER = 0
+MEL_LOG10 = 1
+MEL_LN = 2
+MEL_BINS_FIRST = 0
+MEL_FRAMES_FIRST = 1
 # zflac_hip_batch_decode_buckets: one bit per k_decode history bucket (ZFLAC_BUCKET_*)
 BUCKET_8 = 1
 BUCKET_4 = 2

@@ -4,6 +4,7 @@
 
 #include "batch.h"
 #include "launch.h"
+#include "mel_plan.h"
 
 using namespace zflac;
 
@@ -229,6 +230,19 @@ int zflac_hip_batch_export_resampled_mixed(zflac_batch* b, const zflac_resample_
                                            void* dst_device, size_t dst_bytes, uint64_t* valid_frames, void* stream) {
     return export_dense(b, export_call(d), mix, dst_device, dst_bytes, valid_frames, stream);
 }
+
+int zflac_hip_mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) { return mel_create(d, device, out); }
+
+int zflac_hip_mel_run(zflac_mel* m, const float* wave_device, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
+                      uint64_t first_frame, uint64_t frames, void* dst_device, size_t dst_bytes, void* stream) {
+    return mel_run(m, wave_device, rows, wave_frames, row_stride, first_frame, frames, dst_device, dst_bytes, stream);
+}
+
+uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center) {
+    return mel_frames(n_samples, n_fft, hop, center);
+}
+
+void zflac_hip_mel_destroy(zflac_mel* m) { mel_destroy(m); }
 
 int zflac_hip_batch_resample_tables(zflac_batch* b, uint64_t* built, uint64_t* held_floats) {
     if (!b) return E_INVALID_ARGUMENT;

@@ -249,6 +249,14 @@ void finish_stream_sequential(zflac_batch* b, Class& C, uint32_t slot, const std
 int export_dense(zflac_batch* b, const ExportCall& call, const zflac_mix_desc* mix, void* dst, size_t dst_bytes,
                  uint64_t* valid_frames, void* stream);
 
+// mel_host.cpp
+// The feature plan (zflac_mel: the device tables and the plan's own stream) and its runs; the
+// argument checks, the tables and the grid rule are mel_plan.h's.
+int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out);
+int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
+            uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream);
+void mel_destroy(zflac_mel* m);
+
 }  // namespace zflac
 
 // ---------------------------------------------------------------------------------

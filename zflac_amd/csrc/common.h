@@ -370,4 +370,33 @@ struct ResampleArgs {
     uint32_t vec;          // as ExportArgs::vec, for the rows on k_export's paths
 };
 
+// k_mel (mel.hip): log-mel features of dense f32 rows. A workgroup of MEL_WAVES waves takes
+// MEL_FRAMES feature frames of one row, a wave MEL_TILE of them (the lanes of its MFMA tiles);
+// the frames' samples and the basis go through LDS in slabs of MEL_SLAB samples. The tables'
+// layouts and the grid rule are mel_plan.h's.
+constexpr uint32_t MEL_TILE = 32;                            // edge of an MFMA tile: bins, filters, frames
+constexpr uint32_t MEL_WAVES = 4;
+constexpr uint32_t MEL_THREADS = 64 * MEL_WAVES;
+constexpr uint32_t MEL_FRAMES = MEL_TILE * MEL_WAVES;        // feature frames of a row per workgroup
+constexpr uint32_t MEL_SLAB = 64;                            // samples of every frame staged at a time
+constexpr uint32_t MEL_PAIR_STRIDE = 2 * MEL_FRAMES + 16;    // floats of LDS per sample pair of the staged frames
+constexpr uint32_t MEL_LDS_FLOATS = MEL_SLAB * 2 * MEL_TILE + (MEL_SLAB / 2) * MEL_PAIR_STRIDE;
+
+struct MelArgs {
+    const float* wave;     // rows of row_stride floats
+    const float* basis;    // mel_plan.h: [bin tile][sample pair][re, im][sample of the pair][bin]
+    const float* filters;  // mel_plan.h: [bin tile][accumulator register][filter tile][lane]
+    void* dst;             // rows x n_bins x frames (or rows x frames x n_bins) elements of the dtype
+    uint64_t wave_frames;  // samples of a row; zero outside
+    uint64_t row_stride;
+    uint64_t first_frame;  // feature frame of destination frame 0
+    uint64_t frames;       // destination frames per row
+    uint32_t tiles;        // workgroups per row: ceil(frames / MEL_FRAMES); grid = rows * tiles
+    uint32_t n_fft, hop, off;  // N, hop, center ? N / 2 : 0
+    uint32_t n_bins;       // rows of the filterbank
+    uint32_t bin_tiles;    // ceil((N / 2 + 1) / MEL_TILE)
+    uint32_t scale;        // ZFLAC_MEL_POWER / _LOG10 / _LN
+    float floor;
+};
+
 }  // namespace zflac

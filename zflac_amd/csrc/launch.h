@@ -53,4 +53,7 @@ hipError_t launch_export_mixed(int dtype, int layout, const ExportArgs& a, const
 hipError_t launch_resample(int dtype, int layout, const ResampleArgs& a, hipStream_t st);
 hipError_t launch_resample_mixed(int dtype, int layout, const ResampleArgs& a, const float* coef, hipStream_t st);
 
+// mel.hip: k_mel over rows * a.tiles workgroups; m_tiles is the plan's filter tile count (1, 2, 4 or 8)
+hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st);
+
 }  // namespace zflac

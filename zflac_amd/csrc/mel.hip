@@ -1,0 +1,171 @@
+// mel.hip -- k_mel: log-mel features of dense f32 rows in one launch (zflac_hip_mel_run).
+//
+// Two chained f32 matrix products on the matrix cores (v_mfma_f32_32x32x2_f32, bit for bit an
+// f32 fmaf chain), per tile of frames:
+//   X[2 K x frames] = basis^T [2 K x N] . frames [N x frames]      (re and im of every bin)
+//   V[n_bins x frames] = filters [n_bins x K] . P [K x frames]      P = re^2 + im^2
+// A workgroup of MEL_WAVES waves takes MEL_FRAMES = 128 frames of one row (blockIdx.x =
+// row * tiles + tile), a wave MEL_TILE = 32 of them: the frame is on the lane (l & 31) of every
+// tile the wave holds, bins and filters are on the accumulators' rows. The wave keeps V for all
+// MT filter tiles (MT x 16 registers) and walks the bin tiles; for one bin tile it sums a re and
+// an im accumulator over all N samples, squares them element by element into P, and feeds P's 16
+// registers, each as it stands the B operand of one MFMA (rows r and r + 4 in the two lane
+// halves), into V against the filter table, whose k order mel_plan.cpp has permuted to that map.
+// Nothing crosses lanes and P never leaves the registers.
+//
+// Both operands of the first product come from LDS, in slabs of MEL_SLAB samples:
+//   basis   the slab of the bin tile as mel_plan.cpp laid it out (64 lanes of re, 64 of im per
+//           sample pair): a plain 16-byte copy, read back one float per lane, conflict free. The
+//           four waves share it: every float fetched from L2 feeds 128 frames.
+//   frames  expanded: E[pair][frame][sample of the pair], the frames' samples x[t hop - off + n]
+//           read from the row (zero outside it and for frames past the last) by 8 consecutive
+//           samples of 8 frames per wave and written with MEL_PAIR_STRIDE = 2 * 128 + 16 floats
+//           per pair, which spreads those 64 writes over the 64 banks; a wave's MFMA operand is
+//           then 64 consecutive floats. Expanding costs N / hop times the row's bytes from L1 / L2
+//           and nothing else: it is what lets any hop up to N through one path (a span of
+//           31 hop + N samples does not fit LDS at hop = N = 2048).
+// Every frame's sums run in the same order (n ascending in pairs, bin tiles ascending, registers
+// ascending), whatever lane, wave or workgroup it falls in, so its bits depend on nothing but
+// its samples. Frames past the destination's end are computed from zeros and not stored.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/zflac_hip.h"
+#include "common.h"
+#include "export_tile.h"
+#include "launch.h"
+
+namespace zflac {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <int DT, int LAYOUT, int MT>
+__global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
+    using OT = typename Out<DT>::T;
+    __shared__ __attribute__((aligned(16))) float lds[MEL_LDS_FLOATS];
+    float* const lb = lds;                               // basis slab
+    float* const lf = lds + MEL_SLAB * 2 * MEL_TILE;     // frames slab
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t row = blockIdx.x / a.tiles;
+    const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
+    const float* const x = a.wave + row * a.row_stride;
+    const uint32_t N = a.n_fft;
+
+    // staging of the frames: this thread's sample of every eight and its frame of every 32
+    const uint32_t st_n = tid & 7, st_j = tid >> 3;
+    int64_t st_base[MEL_WAVES];  // sample index of n = 0 of frame st_j + 32 g, or "no frame"
+    bool st_ok[MEL_WAVES];
+#pragma unroll
+    for (uint32_t g = 0; g < MEL_WAVES; g++) {
+        const uint64_t j = j0 + st_j + MEL_TILE * g;
+        st_ok[g] = j < a.frames;
+        st_base[g] = st_ok[g] ? (int64_t)((a.first_frame + j) * a.hop) - (int64_t)a.off : 0;
+    }
+
+    f32x16 V[MT];
+#pragma unroll
+    for (int q = 0; q < MT; q++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) V[q][r] = 0.0f;
+
+    for (uint32_t b = 0; b < a.bin_tiles; b++) {
+        f32x16 re, im;
+#pragma unroll
+        for (int r = 0; r < 16; r++) re[r] = im[r] = 0.0f;
+        const float* const bb = a.basis + (size_t)b * N * (2 * MEL_TILE);
+        for (uint32_t n0 = 0; n0 < N; n0 += MEL_SLAB) {
+            const uint32_t ns = N - n0 < MEL_SLAB ? N - n0 : MEL_SLAB;  // even
+            __syncthreads();  // the last slab has been read
+            const float* const bs = bb + (size_t)n0 * (2 * MEL_TILE);
+            for (uint32_t i = tid * 4; i < ns * (2 * MEL_TILE); i += MEL_THREADS * 4)
+                *reinterpret_cast<f32x4*>(lb + i) = *reinterpret_cast<const f32x4*>(bs + i);
+            for (uint32_t n = st_n; n < ns; n += 8) {
+                float v[MEL_WAVES];
+#pragma unroll
+                for (uint32_t g = 0; g < MEL_WAVES; g++) {
+                    const int64_t s = st_base[g] + (int64_t)(n0 + n);
+                    v[g] = st_ok[g] && s >= 0 && (uint64_t)s < a.wave_frames ? x[s] : 0.0f;
+                }
+#pragma unroll
+                for (uint32_t g = 0; g < MEL_WAVES; g++)
+                    lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
+            }
+            __syncthreads();
+            const float* const pa = lb + lane;
+            const float* const pf = lf + 2 * (wv * MEL_TILE + (lane & 31)) + (lane >> 5);
+            auto pair = [&](uint32_t s) {
+                const float xb = pf[s * MEL_PAIR_STRIDE];
+                re = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[s * 4 * MEL_TILE], xb, re, 0, 0, 0);
+                im = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[s * 4 * MEL_TILE + 2 * MEL_TILE], xb, im, 0, 0, 0);
+            };
+            if (ns == MEL_SLAB) {  // (the same order either way)
+#pragma unroll 8
+                for (uint32_t s = 0; s < MEL_SLAB / 2; s++) pair(s);
+            } else {
+                for (uint32_t s = 0; s < ns / 2; s++) pair(s);
+            }
+        }
+        const float* const fb = a.filters + (size_t)b * (16 * MT * 64) + lane;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float p = __builtin_fmaf(im[r], im[r], re[r] * re[r]);
+#pragma unroll
+            for (int q = 0; q < MT; q++) V[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[(r * MT + q) * 64], p, V[q], 0, 0, 0);
+        }
+    }
+
+    const uint64_t j = j0 + wv * MEL_TILE + (lane & 31);
+    if (j >= a.frames) return;
+    OT* const dst = static_cast<OT*>(a.dst);
+#pragma unroll
+    for (int q = 0; q < MT; q++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t m = q * MEL_TILE + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (m >= a.n_bins) continue;
+            float v = V[q][r];
+            if (a.scale == ZFLAC_MEL_LOG10) v = log10f(fmaxf(v, a.floor));
+            else if (a.scale == ZFLAC_MEL_LN) v = logf(fmaxf(v, a.floor));
+            const uint64_t at = LAYOUT == ZFLAC_MEL_BINS_FIRST ? (row * a.n_bins + m) * a.frames + j
+                                                               : (row * a.frames + j) * a.n_bins + m;
+            dst[at] = conv_f32<DT>(v);
+        }
+}
+
+template <int DT, int LAYOUT>
+hipError_t launch_mt(uint32_t m_tiles, const MelArgs& a, uint32_t blocks, hipStream_t st) {
+    switch (m_tiles) {
+        case 1: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 1>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 2>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 4>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
+        case 8: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 8>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+template <int DT>
+hipError_t launch_dt(int layout, uint32_t m_tiles, const MelArgs& a, uint32_t blocks, hipStream_t st) {
+    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST>(m_tiles, a, blocks, st)
+                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST>(m_tiles, a, blocks, st);
+}
+
+}  // namespace
+
+// rows * a.tiles workgroups (mel_plan_run keeps the product within gridDim.x's 2^31 - 1)
+hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st) {
+    const uint64_t blocks = rows * a.tiles;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    switch (dtype) {
+        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32>(layout, m_tiles, a, (uint32_t)blocks, st);
+        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16>(layout, m_tiles, a, (uint32_t)blocks, st);
+        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16>(layout, m_tiles, a, (uint32_t)blocks, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace zflac

@@ -1,0 +1,107 @@
+// mel_plan.cpp -- see mel_plan.h. Plain C++: tests/c/mel_probe.cpp links this unit alone.
+#include "mel_plan.h"
+
+#include <cmath>
+
+namespace zflac {
+
+int mel_plan_create(const zflac_mel_desc* d, const void* out_ptr, MelPlan& p) {
+    if (!d || !out_ptr) return E_INVALID_ARGUMENT;
+    if (d->size != sizeof(zflac_mel_desc)) return E_INVALID_ARGUMENT;
+    if (d->dtype != ZFLAC_EXPORT_F32 && d->dtype != ZFLAC_EXPORT_F16 && d->dtype != ZFLAC_EXPORT_BF16)
+        return E_INVALID_ARGUMENT;
+    if (d->layout != ZFLAC_MEL_BINS_FIRST && d->layout != ZFLAC_MEL_FRAMES_FIRST) return E_INVALID_ARGUMENT;
+    if (d->scale != ZFLAC_MEL_POWER && d->scale != ZFLAC_MEL_LOG10 && d->scale != ZFLAC_MEL_LN) return E_INVALID_ARGUMENT;
+    if (d->center > 1) return E_INVALID_ARGUMENT;
+    if (d->n_fft < 2 || d->n_fft > MEL_MAX_FFT || (d->n_fft & 1)) return E_INVALID_ARGUMENT;
+    if (d->hop < 1 || d->hop > d->n_fft) return E_INVALID_ARGUMENT;
+    if (d->n_bins < 1 || d->n_bins > MEL_MAX_BINS) return E_INVALID_ARGUMENT;
+    if (d->reserved != 0) return E_INVALID_ARGUMENT;
+    if (d->scale == ZFLAC_MEL_POWER ? d->floor != 0.0f : !(std::isfinite(d->floor) && d->floor > 0.0f))
+        return E_INVALID_ARGUMENT;
+    if (!d->window || !d->filters) return E_INVALID_ARGUMENT;
+    const uint32_t K = d->n_fft / 2u + 1;
+    for (uint32_t n = 0; n < d->n_fft; n++)
+        if (!std::isfinite(d->window[n])) return E_INVALID_ARGUMENT;
+    for (size_t i = 0; i < (size_t)d->n_bins * K; i++)
+        if (!std::isfinite(d->filters[i])) return E_INVALID_ARGUMENT;
+    p.dtype = d->dtype;
+    p.layout = d->layout;
+    p.scale = d->scale;
+    p.center = d->center;
+    p.n_fft = d->n_fft;
+    p.hop = d->hop;
+    p.n_bins = d->n_bins;
+    p.floor = d->floor;
+    p.K = K;
+    p.bin_tiles = (K + MEL_TILE - 1) / MEL_TILE;
+    p.m_tiles = 1;
+    while (p.m_tiles * MEL_TILE < p.n_bins) p.m_tiles *= 2;
+    return E_OK;
+}
+
+size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im) {
+    const size_t b = k / MEL_TILE, i = k % MEL_TILE, s = n / 2, h = n % 2;
+    return (((b * (p.n_fft / 2) + s) * 2 + im) * 2 + h) * MEL_TILE + i;
+}
+
+size_t mel_filter_index(const MelPlan& p, uint32_t m, uint32_t k) {
+    const size_t b = k / MEL_TILE, row = k % MEL_TILE, q = m / MEL_TILE;
+    const size_t h = (row >> 2) & 1;                    // rows 4..7 of every eight sit in lanes 32..63
+    const size_t r = (row & 3) + 4 * (row >> 3);        // mel_acc_row(r) + 4 h == row
+    return ((b * 16 + r) * p.m_tiles + q) * 64 + 32 * h + m % MEL_TILE;
+}
+
+void mel_tables(const MelPlan& p, const float* window, const float* filters, std::vector<float>& basis,
+                std::vector<float>& filt) {
+    const uint32_t N = p.n_fft, K = p.K;
+    basis.assign(p.basis_floats(), 0.0f);
+    filt.assign(p.filter_floats(), 0.0f);
+    std::vector<double> co(N), si(N);
+    const double two_pi = 6.283185307179586476925286766559;
+    for (uint32_t j = 0; j < N; j++) {
+        co[j] = std::cos(two_pi * (double)j / (double)N);
+        si[j] = (2 * j) % N == 0 ? 0.0 : std::sin(two_pi * (double)j / (double)N);  // s[.][0], s[.][N/2]: exactly 0
+    }
+    for (uint32_t n = 0; n < N; n++) {
+        const double w = window[n];
+        for (uint32_t k = 0; k < K; k++) {
+            const uint32_t j = (uint32_t)(((uint64_t)n * k) % N);
+            basis[mel_basis_index(p, n, k, 0)] = (float)(w * co[j]);
+            basis[mel_basis_index(p, n, k, 1)] = (float)(-w * si[j]);
+        }
+    }
+    for (uint32_t m = 0; m < p.n_bins; m++)
+        for (uint32_t k = 0; k < K; k++) filt[mel_filter_index(p, m, k)] = filters[(size_t)m * K + k];
+}
+
+int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
+                 uint64_t first_frame, uint64_t frames, uintptr_t dst, size_t dst_bytes, MelGrid& g) {
+    g = MelGrid{};
+    if (!p || !wave || !dst) return E_INVALID_ARGUMENT;
+    if (wave % sizeof(float)) return E_INVALID_ARGUMENT;
+    if (row_stride < wave_frames) return E_INVALID_ARGUMENT;
+    if (frames == 0) return E_INVALID_ARGUMENT;
+    unsigned __int128 need = (unsigned __int128)rows * p->n_bins;
+    need *= frames;
+    need *= p->elem_size();
+    if (need > (unsigned __int128)dst_bytes) return E_INVALID_ARGUMENT;
+    // every sample index the kernel forms, t * hop - off + n with t < first_frame + frames, is a signed 64-bit value
+    const unsigned __int128 last = ((unsigned __int128)first_frame + frames) * p->hop;
+    if (last >> 63) return E_INVALID_ARGUMENT;
+    // the element offsets into the waveform, (rows - 1) * row_stride + wave_frames, stay below 2^63 too
+    if (rows && ((unsigned __int128)rows * row_stride) >> 61) return E_INVALID_ARGUMENT;
+    const uint64_t tiles = (frames - 1) / MEL_FRAMES + 1;
+    if (tiles > MEL_MAX_GRID || (unsigned __int128)rows * tiles > MEL_MAX_GRID) return E_INVALID_ARGUMENT;
+    g.tiles = (uint32_t)tiles;
+    g.blocks = rows * tiles;
+    return E_OK;
+}
+
+uint64_t mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center) {
+    if (!hop) return 0;
+    if (center) return n_samples ? n_samples / hop + 1 : 0;
+    return n_samples >= n_fft ? (n_samples - n_fft) / hop + 1 : 0;
+}
+
+}  // namespace zflac

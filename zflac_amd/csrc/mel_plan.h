@@ -1,0 +1,75 @@
+// mel_plan.h -- host planning of the log-mel features (zflac_hip_mel_create / _run, k_mel): the
+// argument checks of both calls, the tables in the layout the kernel reads, the grid rule and the
+// frame count. Plain C++ (mel_plan.cpp), no HIP.
+//
+// The definition is include/zflac_hip.h's: N = n_fft, K = N / 2 + 1,
+//   re[k] = sum_n c[n][k] x[t hop - off + n],  im[k] = sum_n s[n][k] x[...],  P = re^2 + im^2,
+//   v[m] = sum_k filters[m][k] P[k].
+// k_mel computes both sums with the f32 MFMA v_mfma_f32_32x32x2_f32 (a 32 x 32 tile, two terms
+// of the sum per instruction: lanes 0..31 carry the first, lanes 32..63 the second), so the
+// tables are cut into tiles of MEL_TILE = 32 and laid out lane by lane:
+//
+//   basis    [bin tile b][sample pair s][re, im][h = sample of the pair][i = bin of the tile]
+//            = c or s [2 s + h][32 b + i], zero for bins >= K. The 64 floats of one (b, s, re/im)
+//            are the A operand of one MFMA, lane l = 32 h + i; a tile's N / 2 pairs are
+//            contiguous, so a slab of it goes to LDS as a plain copy. N is even: no padding in n.
+//   filters  [bin tile b][register r][filter tile q][lane l]
+//            = filters[32 q + (l & 31)][32 b + mel_acc_row(r) + 4 (l >> 5)], zero for filters
+//            >= n_bins and bins >= K. Register r of a 32 x 32 accumulator holds row mel_acc_row(r)
+//            of the tile in lanes 0..31 and that row + 4 in lanes 32..63: P's register r is the
+//            B operand of one MFMA as it stands, against this A operand.
+//            The filter tiles are m_tiles = 1, 2, 4 or 8 (the least that holds n_bins).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/zflac_hip.h"
+#include "common.h"
+
+namespace zflac {
+
+constexpr uint32_t MEL_MAX_FFT = 2048;
+constexpr uint32_t MEL_MAX_BINS = 256;
+constexpr uint64_t MEL_MAX_GRID = 0x7FFFFFFFull;  // gridDim.x
+
+struct MelPlan {
+    uint8_t dtype = 0, layout = 0, scale = 0, center = 0;
+    uint32_t n_fft = 0, hop = 0, n_bins = 0;
+    float floor = 0;
+    uint32_t K = 0;          // N / 2 + 1
+    uint32_t bin_tiles = 0;  // ceil(K / MEL_TILE)
+    uint32_t m_tiles = 0;    // filter tiles: 1, 2, 4 or 8
+    size_t basis_floats() const { return (size_t)bin_tiles * n_fft * 2 * MEL_TILE; }
+    size_t filter_floats() const { return (size_t)bin_tiles * 16 * m_tiles * 64; }
+    size_t elem_size() const { return dtype == ZFLAC_EXPORT_F32 ? 4 : 2; }
+};
+
+// Row of a 32 x 32 MFMA accumulator that register r holds in lanes 0..31 (lanes 32..63: + 4).
+constexpr uint32_t mel_acc_row(uint32_t r) { return (r & 3) + 8 * (r >> 2); }
+
+// zflac_hip_mel_create's checks, in this order: d and out (out_ptr: the caller's `out`, only
+// compared with NULL); size; dtype, layout, scale, center; n_fft; hop; n_bins; reserved; floor;
+// window and filters (NULL, then every value finite). E_OK fills p; nothing else is touched.
+int mel_plan_create(const zflac_mel_desc* d, const void* out_ptr, MelPlan& p);
+
+// Where the kernel's tables hold c[n][k] (im = 0) or s[n][k] (im = 1), and filters[m][k]
+size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im);
+size_t mel_filter_index(const MelPlan& p, uint32_t m, uint32_t k);
+// Both tables, p.basis_floats() and p.filter_floats() long, zero wherever no (n, k) or (m, k) lands
+void mel_tables(const MelPlan& p, const float* window, const float* filters, std::vector<float>& basis,
+                std::vector<float>& filt);
+
+struct MelGrid {
+    uint32_t tiles = 0;   // workgroups per row: ceil(frames / MEL_FRAMES)
+    uint64_t blocks = 0;  // rows * tiles
+};
+// zflac_hip_mel_run's checks, in this order: p (the plan, NULL = no plan), wave, dst; wave's
+// alignment; row_stride; frames; dst_bytes; (first_frame + frames) * hop; the grid. rows == 0 is
+// E_OK with g.blocks == 0 once the checks that do not involve rows have passed.
+int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
+                 uint64_t first_frame, uint64_t frames, uintptr_t dst, size_t dst_bytes, MelGrid& g);
+
+uint64_t mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center);
+
+}  // namespace zflac

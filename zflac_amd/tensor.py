@@ -1,6 +1,8 @@
 """Decoded batches as dense torch tensors on the GPU (zflac_hip_batch_export, k_export; at one
 sample rate with sample_rate=: zflac_hip_batch_export_resampled, k_resample; with the channels
-mixed on the device with mix=: zflac_hip_batch_export_mixed / _export_resampled_mixed).
+mixed on the device with mix=: zflac_hip_batch_export_mixed / _export_resampled_mixed), and
+log-mel features of such a tensor in one more launch (MelSpectrogram, decode_to_features:
+zflac_hip_mel_run, k_mel).
 
     import torch                      # before zflac_amd loads its library (see below)
     from zflac_amd import Batch, tensor
@@ -253,6 +255,222 @@ def export(batch: Batch, frames=None, channels=None, starts=None, dtype=torch.fl
     errors.check(rc, "batch_export")
     lengths = torch.tensor(list(valid)[:n], dtype=torch.int64).to(dev)
     return out, lengths
+
+
+def mel_filters(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="slaney", norm="slaney"):
+    """A triangular mel filterbank -> numpy float32 [n_mels, n_fft // 2 + 1]. Pure numpy, no GPU.
+
+    The mel scale, f in Hz:
+      "htk":    mel(f) = 2595 log10(1 + f / 700),            f(mel) = 700 (10^(mel / 2595) - 1)
+      "slaney": mel(f) = 3 f / 200 for f < 1000, else 15 + 27 ln(f / 1000) / ln(6.4)
+                f(mel) = 200 mel / 3 for mel < 15, else 1000 exp((mel - 15) ln(6.4) / 27)
+    n_mels + 2 points p_0 .. p_{n_mels + 1} lie equally spaced in mel from mel(f_min) to mel(f_max)
+    (f_max defaults to sample_rate / 2) and are taken back to Hz. With f_k = k sample_rate / n_fft
+    the frequency of bin k, filter m is the triangle over [p_m, p_{m + 2}] with its peak, 1, at
+    p_{m + 1}:
+      w[m][k] = max(0, min((f_k - p_m) / (p_{m + 1} - p_m), (p_{m + 2} - f_k) / (p_{m + 2} - p_{m + 1})))
+    norm="slaney" scales row m by 2 / (p_{m + 2} - p_m) (unit area per filter); norm=None leaves the
+    peaks at 1. Everything is computed in float64 and rounded once. (sample_rate 16000, n_fft 400,
+    n_mels 80 with the defaults are the filters Whisper's front end uses.)"""
+    import numpy as np
+
+    n_fft, n_mels = int(n_fft), int(n_mels)
+    if n_fft < 2 or n_fft % 2 or n_mels < 1:
+        raise ValueError("n_fft even and >= 2, n_mels >= 1")
+    f_max = sample_rate / 2.0 if f_max is None else float(f_max)
+    f_min = float(f_min)
+    if not 0.0 <= f_min < f_max:
+        raise ValueError("0 <= f_min < f_max")
+    if mel_scale == "htk":
+        def to_mel(f):
+            return 2595.0 * np.log10(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+        def to_hz(m):
+            return 700.0 * (10.0 ** (np.asarray(m, dtype=np.float64) / 2595.0) - 1.0)
+    elif mel_scale == "slaney":
+        step = np.log(6.4) / 27.0
+
+        def to_mel(f):
+            f = np.asarray(f, dtype=np.float64)
+            return np.where(f < 1000.0, 3.0 * f / 200.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / step)
+
+        def to_hz(m):
+            m = np.asarray(m, dtype=np.float64)
+            return np.where(m < 15.0, 200.0 * m / 3.0, 1000.0 * np.exp((m - 15.0) * step))
+    else:
+        raise ValueError("mel_scale is 'slaney' or 'htk'")
+    if norm not in ("slaney", None):
+        raise ValueError("norm is 'slaney' or None")
+    p = to_hz(np.linspace(to_mel(f_min), to_mel(f_max), n_mels + 2))
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * (float(sample_rate) / n_fft)
+    lower = (f[None, :] - p[:-2, None]) / (p[1:-1] - p[:-2])[:, None]
+    upper = (p[2:, None] - f[None, :]) / (p[2:] - p[1:-1])[:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper))
+    if norm == "slaney":
+        w *= (2.0 / (p[2:] - p[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+_MEL_SCALES = {"power": _lib.MEL_POWER, "log10": _lib.MEL_LOG10, "ln": _lib.MEL_LN}
+_MEL_LAYOUTS = {"bins_first": _lib.MEL_BINS_FIRST, "frames_first": _lib.MEL_FRAMES_FIRST}
+
+
+class MelSpectrogram:
+    """Log-mel features of f32 waveforms on the GPU in one launch (zflac_hip_mel_run, k_mel).
+
+        mel = MelSpectrogram(16000)                     # n_fft 400, hop 160, 80 mel bins, log10
+        feats, feat_lengths = mel(x, lengths)           # x: [B, T] or [B, C, T] float32 on cuda
+
+    window: "hann" (periodic, 0.5 - 0.5 cos(2 pi n / n_fft)) or n_fft values. filters: an array
+    [n_bins, n_fft // 2 + 1], or None for mel_filters(sample_rate, n_fft, n_mels, **filter_kw).
+    scale: "log10" or "ln" of max(v, floor), or "power" (the sums themselves; floor is not used).
+    center: frame t starts at sample t hop - n_fft / 2 (else at t hop); samples outside a row are
+    zero. There is no reflect padding: the first and last n_fft / (2 hop) frames differ from
+    torch.stft's default. The object owns a plan of the library: close() it, or use it in `with`."""
+
+    def __init__(self, sample_rate, n_fft=400, hop=160, n_mels=80, window="hann", filters=None, scale="log10",
+                 floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, **filter_kw):
+        import numpy as np
+
+        check_single_runtime()
+        if dtype not in _DTYPES or dtype == torch.int32:
+            raise TypeError("dtype is float32, float16 or bfloat16")
+        if scale not in _MEL_SCALES:
+            raise ValueError("scale is 'log10', 'ln' or 'power'")
+        if layout not in _MEL_LAYOUTS:
+            raise ValueError("layout is 'bins_first' or 'frames_first'")
+        n_fft, hop = int(n_fft), int(hop)
+        if not (2 <= n_fft <= 2048 and n_fft % 2 == 0 and 1 <= hop <= n_fft):
+            raise ValueError("n_fft even in 2..2048, 1 <= hop <= n_fft")
+        if isinstance(window, str):
+            if window != "hann":
+                raise ValueError("window is 'hann' or an array of n_fft values")
+            w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft)).astype(np.float32)
+        else:
+            w = np.ascontiguousarray(window.detach().cpu().numpy() if isinstance(window, torch.Tensor) else window,
+                                     dtype=np.float32)
+        if w.shape != (n_fft,):
+            raise ValueError(f"window has shape {w.shape}, expected {(n_fft,)}")
+        if filters is None:
+            fb = mel_filters(sample_rate, n_fft, n_mels, **filter_kw)
+        else:
+            if filter_kw:
+                raise TypeError(f"with filters=, unexpected {sorted(filter_kw)}")
+            fb = np.ascontiguousarray(filters.detach().cpu().numpy() if isinstance(filters, torch.Tensor) else filters,
+                                      dtype=np.float32)
+        if fb.ndim != 2 or fb.shape[1] != n_fft // 2 + 1 or not 1 <= fb.shape[0] <= 256:
+            raise ValueError(f"filters have shape {fb.shape}, expected (1..256, {n_fft // 2 + 1})")
+        self.sample_rate, self.n_fft, self.hop, self.n_bins = sample_rate, n_fft, hop, int(fb.shape[0])
+        self.center, self.dtype, self.layout, self.scale, self.device = bool(center), dtype, layout, scale, int(device)
+        self.floor = 0.0 if scale == "power" else float(floor)
+        self.window, self.filters = w, fb
+        self._L = _lib.load()
+        desc = _lib.zflac_mel_desc(ctypes.sizeof(_lib.zflac_mel_desc), _DTYPES[dtype], _MEL_LAYOUTS[layout],
+                                   _MEL_SCALES[scale], int(self.center), n_fft, hop, self.n_bins, 0, self.floor,
+                                   w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                   fb.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+        self._h = ctypes.c_void_p()
+        errors.check(self._L.zflac_hip_mel_create(ctypes.byref(desc), self.device, ctypes.byref(self._h)), "mel_create")
+
+    def mel_frames(self, n_samples):
+        """Frames of a row of n_samples (zflac_hip_mel_frames): an int, or a tensor for a tensor."""
+        if isinstance(n_samples, torch.Tensor):
+            n = n_samples.to(torch.int64)
+            if self.center:
+                return torch.where(n > 0, n // self.hop + 1, torch.zeros_like(n))
+            return torch.where(n >= self.n_fft, (n - self.n_fft) // self.hop + 1, torch.zeros_like(n))
+        return int(self._L.zflac_hip_mel_frames(int(n_samples), self.n_fft, self.hop, int(self.center)))
+
+    def __call__(self, x, lengths=None, frames=None, first_frame=0, out=None, stream=None):
+        """x: contiguous float32 [B, T] or [B, C, T] on cuda:<device>; lengths: valid samples per
+        batch row (default T) -> (features, feature_lengths). features: [B, (C,) n_bins, frames]
+        (layout="bins_first") or [B, (C,) frames, n_bins], frame j of it being feature frame
+        first_frame + j; frames defaults to mel_frames(T) - first_frame. feature_lengths: int64
+        [B], clamp(mel_frames(lengths) - first_frame, 0, frames). Enqueued on `stream` (default:
+        torch's current stream of the device); nothing is synchronised."""
+        check_single_runtime()
+        if self._h is None:
+            raise ValueError("the plan is closed")
+        dev = torch.device("cuda", self.device)
+        if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype != torch.float32:
+            raise TypeError(f"x must be a float32 tensor on {dev}")
+        if x.dim() not in (2, 3) or not x.is_contiguous():
+            raise ValueError("x must be contiguous [B, T] or [B, C, T]")
+        T = int(x.shape[-1])
+        first_frame = int(first_frame)
+        if first_frame < 0:
+            raise ValueError("first_frame >= 0")
+        if frames is None:
+            frames = max(self.mel_frames(T) - first_frame, 1)
+        frames = int(frames)
+        if frames < 1:
+            raise ValueError("frames >= 1")
+        lead = tuple(x.shape[:-1])
+        shape = lead + ((self.n_bins, frames) if self.layout == "bins_first" else (frames, self.n_bins))
+        if out is None:
+            out = torch.empty(shape, dtype=self.dtype, device=dev)
+        else:
+            if not isinstance(out, torch.Tensor) or out.device != dev:
+                raise ValueError(f"out must be a tensor on {dev}")
+            if out.dtype != self.dtype:
+                raise TypeError(f"out.dtype is {out.dtype}, expected {self.dtype}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out.shape is {tuple(out.shape)}, expected {shape}")
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+        if lengths is None:
+            lengths = torch.full((int(x.shape[0]),), T, dtype=torch.int64, device=dev)
+        else:
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+            if tuple(lengths.shape) != (int(x.shape[0]),):
+                raise ValueError("lengths: one per batch row")
+        feature_lengths = torch.clamp(self.mel_frames(lengths) - first_frame, 0, frames)
+        rows = 1
+        for n in lead:
+            rows *= int(n)
+        if rows == 0:
+            return out, feature_lengths
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        if not stream.cuda_stream:
+            stream.synchronize()  # the null stream has no handle: the plan's own stream, complete on return
+        rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, out.data_ptr(),
+                                       out.numel() * out.element_size(), stream.cuda_stream or None)
+        errors.check(rc, "mel_run")
+        return out, feature_lengths
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._L.zflac_hip_mel_destroy(self._h)  # waits for the device
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def decode_to_features(streams, mel: MelSpectrogram, device: int = 0, mix="mono", **export_kw):
+    """Decode `streams`, export them at mel.sample_rate with the channels mixed (decode_to_tensor,
+    float32) and take the features of that tensor -> (features, feature_lengths, infos). features:
+    [B, channels, n_bins, frames]; the row of a stream that ended in an error is the constant an
+    all-zero row gives, with length 0. Complete when this returns."""
+    if mel.device != device:
+        raise ValueError(f"the plan is on device {mel.device}, not {device}")
+    if export_kw.get("dtype", torch.float32) != torch.float32 or export_kw.get("layout", "planar") != "planar":
+        raise TypeError("the features are taken from a planar float32 export")
+    x, lengths, infos = decode_to_tensor(streams, device, sample_rate=mel.sample_rate, mix=mix, **export_kw)
+    stream = export_kw.get("stream") or torch.cuda.current_stream(x.device)
+    feats, feature_lengths = mel(x, lengths, stream=stream)
+    stream.synchronize()
+    return feats, feature_lengths, infos
 
 
 def decode_to_tensor(streams, device: int = 0, **kw):
