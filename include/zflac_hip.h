@@ -373,7 +373,8 @@ int zflac_hip_batch_export_resampled_mixed(zflac_batch *b, const zflac_resample_
  * so v = +0 and a log output of exactly log(floor). Every element of the destination is written.
  *
  * Padding is zeros only. There is no reflect mode: with center = 1 the first and the last
- * N / (2 hop) frames differ from those of a reflect-padded STFT (torch.stft's default). */
+ * N / (2 hop) frames differ from those of a reflect-padded STFT (torch.stft's default). That
+ * holds for zflac_hip_mel_run; zflac_hip_mel_run_ex below has ZFLAC_PAD_REFLECT. */
 #define ZFLAC_MEL_POWER 0   /* the filterbank sums as they are */
 #define ZFLAC_MEL_LOG10 1   /* log10f(max(v, floor)) */
 #define ZFLAC_MEL_LN    2   /* logf(max(v, floor)) */
@@ -412,6 +413,73 @@ int zflac_hip_mel_create(const zflac_mel_desc *d, int device, zflac_mel **out);
 int zflac_hip_mel_run(zflac_mel *m, const float *wave_device, uint64_t rows, uint64_t wave_frames,
                       uint64_t row_stride, uint64_t first_frame, uint64_t frames,
                       void *dst_device, size_t dst_bytes, void *stream);
+/* zflac_hip_mel_run with three more things a front end like Whisper's needs: a length per row,
+ * reflect padding (torch.stft's default) and the clamp to the row maximum with an affine map
+ * behind it. The plan, the tables and the sums are zflac_hip_mel_run's.
+ *
+ * Row length. n_i = min(lengths_device[i], wave_frames), or wave_frames for every row when
+ * lengths_device is NULL. Nothing at or past x_i[n_i] is ever read as signal.
+ *
+ * ZFLAC_PAD_ZEROS: the definition above with n_i in place of wave_frames.
+ * ZFLAC_PAD_REFLECT (a plan with center = 1 only): the frame sums read xr_i[s] in place of x_i[s],
+ *   xr_i[s] = x_i[rho(s)]  for -N/2 <= s < n_i + N/2 and 0 <= rho(s) < n_i, and 0 otherwise,
+ *   rho(s) = -s for s < 0,  2 (n_i - 1) - s for s >= n_i,  s otherwise.
+ * One reflection, a total function: for n_i > N/2 it is numpy.pad(mode="reflect") and torch.stft's
+ * padding by N/2; for n_i <= N/2 (0 and 1 included) it is still defined, so no length is checked
+ * on the host. A row with n_i = 0 is all zeros. Frames at or past zflac_hip_mel_frames(n_i, ...)
+ * are still computed, from xr_i.
+ * The order of every sum is that of zflac_hip_mel_run and a frame's bits depend only on the N
+ * values under it: a frame whose span lies inside [0, n_i) has the same bits in both pad modes,
+ * and a reflect run of a row equals a zeros run of an uncentred plan with the same tables over
+ * that row padded by reflection on the host.
+ *
+ * row_max_device != NULL: element i receives M_i, the maximum over the n_bins x frames elements
+ * of row i that this call writes of the f32 value before it is rounded to the destination dtype
+ * (v, or its log); the same bits for every dtype and layout. A maximum does not depend on the
+ * order it is taken in, so M_i is deterministic. A NaN among the values is skipped (fmaxf).
+ *
+ * ZFLAC_NORM_ROW_MAX (needs row_max_device, a log scale, finite range >= 0, finite add, finite
+ * mul != 0): with l the value ZFLAC_NORM_NONE would have stored (rounded to the destination
+ * dtype, then widened to f32 again) the element stored is
+ *   conv( (fmaxf(l, M_i - range) + add) * mul )
+ * where the subtraction, the addition and the product are one f32 rounding each and nothing is
+ * fused. For an f32 destination that is the single-rounding formula; for f16 / bf16 the value is
+ * rounded to the dtype twice, once before the clamp and once after the product: a defined double
+ * rounding, the one a caller who normalises a stored f16 / bf16 tensor gets. Whisper's input is
+ * range = 8, add = 4, mul = 0.25 ((x + 4) / 4 in the same bits). M_i is taken over the window
+ * [first_frame, first_frame + frames) this call asks for, so normalised outputs, unlike all
+ * others, depend on the window. With ZFLAC_NORM_NONE range, add and mul must be 0.
+ *
+ * pad = ZFLAC_PAD_ZEROS, norm = ZFLAC_NORM_NONE, lengths_device = row_max_device = NULL is
+ * zflac_hip_mel_run in every respect: the same kernel, the same bits, the same errors.
+ *
+ * Stream semantics are zflac_hip_mel_run's. The call enqueues up to three things on the one
+ * stream (a fill of row_max_device with -inf, k_mel, the normalising pass k_mel_norm) and stages
+ * nothing from the host; row_max_device belongs to the caller, so runs of one plan on different
+ * streams with different row_max_device may overlap. rows == 0: ZFLAC_OK, nothing done.
+ * ZFLAC_E_INVALID_ARGUMENT (nothing enqueued): NULL m or r; a wrong size; an unknown pad or norm;
+ * reserved or reserved2 != 0; everything zflac_hip_mel_run refuses; lengths_device not 8-byte or
+ * row_max_device not 4-byte aligned; ZFLAC_PAD_REFLECT with an uncentred plan; ZFLAC_NORM_ROW_MAX
+ * outside its rule above; non-zero range, add or mul with ZFLAC_NORM_NONE. */
+#define ZFLAC_PAD_ZEROS   0
+#define ZFLAC_PAD_REFLECT 1
+#define ZFLAC_NORM_NONE    0
+#define ZFLAC_NORM_ROW_MAX 1
+typedef struct zflac_mel_run_desc {
+    uint32_t size;                  /* sizeof(zflac_mel_run_desc): 104 on LP64 */
+    uint8_t pad, norm;              /* ZFLAC_PAD_*, ZFLAC_NORM_* */
+    uint16_t reserved;              /* must be 0 */
+    const float *wave_device;
+    uint64_t rows, wave_frames, row_stride;  /* as zflac_hip_mel_run */
+    const uint64_t *lengths_device; /* device, one per row, or NULL: wave_frames for every row */
+    uint64_t first_frame, frames;
+    void *dst_device;
+    size_t dst_bytes;
+    float *row_max_device;          /* device, `rows` floats, written; or NULL */
+    float range, add, mul;          /* ZFLAC_NORM_ROW_MAX; else 0 */
+    uint32_t reserved2;             /* must be 0 */
+} zflac_mel_run_desc;
+int zflac_hip_mel_run_ex(zflac_mel *m, const zflac_mel_run_desc *r, void *stream);
 /* Frames of a centred (n ? n / hop + 1 : 0) or uncentred (n >= n_fft ? (n - n_fft) / hop + 1 : 0)
  * STFT of n_samples: what callers use as the valid length. 0 when hop is 0. Host arithmetic. */
 uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center);
@@ -475,7 +543,8 @@ const char *zflac_hip_build_id(void);
  *    zflac_hip_batch_front, ZFLAC_FRONT_*, ZFLAC_FLAG_FRONT_*; zflac_mix_desc,
  *    ZFLAC_MIX_MAX_CHANNELS, zflac_hip_batch_export_mixed, zflac_hip_batch_export_resampled_mixed;
  *    zflac_mel_desc, zflac_mel, ZFLAC_MEL_*, zflac_hip_mel_create, zflac_hip_mel_run,
- *    zflac_hip_mel_frames, zflac_hip_mel_destroy. */
+ *    zflac_hip_mel_frames, zflac_hip_mel_destroy; zflac_mel_run_desc, zflac_hip_mel_run_ex,
+ *    ZFLAC_PAD_*, ZFLAC_NORM_*. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

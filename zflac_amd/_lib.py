@@ -58,6 +58,15 @@ class zflac_mel_desc(ctypes.Structure):
                 ("filters", ctypes.POINTER(ctypes.c_float))]
 
 
+class zflac_mel_run_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("pad", ctypes.c_uint8), ("norm", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16), ("wave_device", ctypes.c_void_p), ("rows", ctypes.c_uint64),
+                ("wave_frames", ctypes.c_uint64), ("row_stride", ctypes.c_uint64), ("lengths_device", ctypes.c_void_p),
+                ("first_frame", ctypes.c_uint64), ("frames", ctypes.c_uint64), ("dst_device", ctypes.c_void_p),
+                ("dst_bytes", ctypes.c_size_t), ("row_max_device", ctypes.c_void_p), ("range", ctypes.c_float),
+                ("add", ctypes.c_float), ("mul", ctypes.c_float), ("reserved2", ctypes.c_uint32)]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -97,6 +106,7 @@ SIGNATURES = {
     "zflac_hip_mel_create": (ctypes.c_int, [ctypes.POINTER(zflac_mel_desc), ctypes.c_int, ctypes.POINTER(_P)]),
     "zflac_hip_mel_run": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_uint64, _P, ctypes.c_size_t, _P]),
+    "zflac_hip_mel_run_ex": (ctypes.c_int, [_P, ctypes.POINTER(zflac_mel_run_desc), _P]),
     "zflac_hip_mel_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
     "zflac_hip_mel_destroy": (None, [_P]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
@@ -132,6 +142,11 @@ MEL_LOG10 = 1
 MEL_LN = 2
 MEL_BINS_FIRST = 0
 MEL_FRAMES_FIRST = 1
+# zflac_mel_run_desc: padding and normalisation of a run (ZFLAC_PAD_*, ZFLAC_NORM_*)
+PAD_ZEROS = 0
+PAD_REFLECT = 1
+NORM_NONE = 0
+NORM_ROW_MAX = 1
 # zflac_hip_batch_decode_buckets: one bit per k_decode history bucket (ZFLAC_BUCKET_*)
 BUCKET_8 = 1
 BUCKET_4 = 2

@@ -238,6 +238,8 @@ int zflac_hip_mel_run(zflac_mel* m, const float* wave_device, uint64_t rows, uin
     return mel_run(m, wave_device, rows, wave_frames, row_stride, first_frame, frames, dst_device, dst_bytes, stream);
 }
 
+int zflac_hip_mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) { return mel_run_ex(m, r, stream); }
+
 uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center) {
     return mel_frames(n_samples, n_fft, hop, center);
 }

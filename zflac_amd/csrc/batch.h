@@ -255,6 +255,7 @@ int export_dense(zflac_batch* b, const ExportCall& call, const zflac_mix_desc* m
 int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out);
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream);
+int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream);
 void mel_destroy(zflac_mel* m);
 
 }  // namespace zflac

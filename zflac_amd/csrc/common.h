@@ -399,4 +399,24 @@ struct MelArgs {
     float floor;
 };
 
+// What zflac_hip_mel_run_ex adds to a launch of k_mel (its EX instantiations), and k_mel_norm.
+struct MelExArgs {
+    MelArgs a;
+    const uint64_t* lengths;  // per row, clamped to a.wave_frames; NULL = a.wave_frames
+    float* row_max;           // per row, -inf before the launch; NULL = not wanted
+    uint32_t pad;             // ZFLAC_PAD_ZEROS / _REFLECT
+};
+
+constexpr uint32_t MEL_NORM_THREADS = 256;
+constexpr uint32_t MEL_NORM_CHUNK = 4096;  // elements of one row per workgroup pass
+
+struct MelNormArgs {
+    void* dst;             // rows x row_elems elements of the dtype (either layout: a row is contiguous)
+    const float* row_max;
+    uint64_t row_elems;    // n_bins * frames
+    uint64_t chunks;       // per row: ceil(row_elems / MEL_NORM_CHUNK)
+    uint64_t total;        // rows * chunks
+    float range, add, mul;
+};
+
 }  // namespace zflac

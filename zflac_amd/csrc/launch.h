@@ -55,5 +55,8 @@ hipError_t launch_resample_mixed(int dtype, int layout, const ResampleArgs& a, c
 
 // mel.hip: k_mel over rows * a.tiles workgroups; m_tiles is the plan's filter tile count (1, 2, 4 or 8)
 hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st);
+// k_mel_ex (lengths, reflect padding, the row maximum) over the same grid; k_mel_norm over a.total passes
+hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, const MelExArgs& e, uint64_t rows, hipStream_t st);
+hipError_t launch_mel_norm(int dtype, const MelNormArgs& a, hipStream_t st);
 
 }  // namespace zflac

@@ -1,4 +1,6 @@
-// mel.hip -- k_mel: log-mel features of dense f32 rows in one launch (zflac_hip_mel_run).
+// mel.hip -- k_mel: log-mel features of dense f32 rows in one launch (zflac_hip_mel_run); k_mel_ex
+// and k_mel_norm: the same with per-row lengths, reflect padding, the row maximum and the clamp to
+// it (zflac_hip_mel_run_ex).
 //
 // Two chained f32 matrix products on the matrix cores (v_mfma_f32_32x32x2_f32, bit for bit an
 // f32 fmaf chain), per tile of frames:
@@ -27,6 +29,15 @@
 // Every frame's sums run in the same order (n ascending in pairs, bin tiles ascending, registers
 // ascending), whatever lane, wave or workgroup it falls in, so its bits depend on nothing but
 // its samples. Frames past the destination's end are computed from zeros and not stored.
+//
+// zflac_hip_mel_run_ex launches k_mel_ex, the same tile with three additions that leave every
+// sum as it is: the row's own length n_i (one uniform load), reflect padding, and the row
+// maximum. Only the staging of E knows about padding: a workgroup decides once whether its tile is
+// interior (every sample index of its 128 frames inside [0, n_i)) and then stages exactly as
+// k_mel does; the first tile, the tiles around a row's end and those past it take a second loop
+// that reads x[rho(s)]. The epilogue takes the maximum of the f32 values a lane stores, a wave
+// reduces it and one atomic per wave goes to row_max[row] (-inf before the launch). k_mel_norm is
+// the elementwise pass behind it (ZFLAC_NORM_ROW_MAX).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,8 +53,10 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int DT, int LAYOUT, int MT>
-__global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
+// One workgroup's tile. EX = false is zflac_hip_mel_run's kernel as it always was; EX = true
+// (zflac_hip_mel_run_ex) adds the row's own length, reflect padding and the row maximum.
+template <int DT, int LAYOUT, int MT, bool EX>
+__device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengths, float* row_max, uint32_t pad) {
     using OT = typename Out<DT>::T;
     __shared__ __attribute__((aligned(16))) float lds[MEL_LDS_FLOATS];
     float* const lb = lds;                               // basis slab
@@ -53,6 +66,20 @@ __global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
     const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
     const float* const x = a.wave + row * a.row_stride;
     const uint32_t N = a.n_fft;
+    // the row's length, and whether this tile needs the reflection: both uniform, decided once.
+    // An interior tile (every sample index of its 128 frames inside [0, n_row)) stages as ever.
+    uint64_t n_row = a.wave_frames;
+    bool edge = false;
+    if constexpr (EX) {
+        if (lengths) {
+            const uint64_t n = lengths[row];
+            n_row = n < a.wave_frames ? n : a.wave_frames;
+        }
+        if (pad == ZFLAC_PAD_REFLECT) {
+            const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - (int64_t)a.off;
+            edge = lo < 0 || (uint64_t)lo + (uint64_t)(MEL_FRAMES - 1) * a.hop + N > n_row;
+        }
+    }
 
     // staging of the frames: this thread's sample of every eight and its frame of every 32
     const uint32_t st_n = tid & 7, st_j = tid >> 3;
@@ -82,16 +109,32 @@ __global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
             const float* const bs = bb + (size_t)n0 * (2 * MEL_TILE);
             for (uint32_t i = tid * 4; i < ns * (2 * MEL_TILE); i += MEL_THREADS * 4)
                 *reinterpret_cast<f32x4*>(lb + i) = *reinterpret_cast<const f32x4*>(bs + i);
-            for (uint32_t n = st_n; n < ns; n += 8) {
-                float v[MEL_WAVES];
+            if (EX && edge) {  // x~[s] = x[rho(s)]: one reflection about 0 or n_row - 1, zero beyond it
+                const int64_t nr = (int64_t)n_row, half = (int64_t)(N / 2);
+                for (uint32_t n = st_n; n < ns; n += 8) {
+                    float v[MEL_WAVES];
 #pragma unroll
-                for (uint32_t g = 0; g < MEL_WAVES; g++) {
-                    const int64_t s = st_base[g] + (int64_t)(n0 + n);
-                    v[g] = st_ok[g] && s >= 0 && (uint64_t)s < a.wave_frames ? x[s] : 0.0f;
+                    for (uint32_t g = 0; g < MEL_WAVES; g++) {
+                        const int64_t s = st_base[g] + (int64_t)(n0 + n);
+                        const int64_t r = s < 0 ? -s : (s >= nr ? 2 * (nr - 1) - s : s);
+                        v[g] = st_ok[g] && s >= -half && s < nr + half && r >= 0 && r < nr ? x[r] : 0.0f;
+                    }
+#pragma unroll
+                    for (uint32_t g = 0; g < MEL_WAVES; g++)
+                        lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
                 }
+            } else {
+                for (uint32_t n = st_n; n < ns; n += 8) {
+                    float v[MEL_WAVES];
 #pragma unroll
-                for (uint32_t g = 0; g < MEL_WAVES; g++)
-                    lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
+                    for (uint32_t g = 0; g < MEL_WAVES; g++) {
+                        const int64_t s = st_base[g] + (int64_t)(n0 + n);
+                        v[g] = st_ok[g] && s >= 0 && (uint64_t)s < n_row ? x[s] : 0.0f;
+                    }
+#pragma unroll
+                    for (uint32_t g = 0; g < MEL_WAVES; g++)
+                        lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
+                }
             }
             __syncthreads();
             const float* const pa = lb + lane;
@@ -118,54 +161,162 @@ __global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
     }
 
     const uint64_t j = j0 + wv * MEL_TILE + (lane & 31);
-    if (j >= a.frames) return;
+    if constexpr (!EX) {
+        if (j >= a.frames) return;
+    }
     OT* const dst = static_cast<OT*>(a.dst);
+    float mx = -__builtin_inff();  // of the f32 values this lane stores
+    if (j < a.frames) {
 #pragma unroll
-    for (int q = 0; q < MT; q++)
+        for (int q = 0; q < MT; q++)
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t m = q * MEL_TILE + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (m >= a.n_bins) continue;
-            float v = V[q][r];
-            if (a.scale == ZFLAC_MEL_LOG10) v = log10f(fmaxf(v, a.floor));
-            else if (a.scale == ZFLAC_MEL_LN) v = logf(fmaxf(v, a.floor));
-            const uint64_t at = LAYOUT == ZFLAC_MEL_BINS_FIRST ? (row * a.n_bins + m) * a.frames + j
-                                                               : (row * a.frames + j) * a.n_bins + m;
-            dst[at] = conv_f32<DT>(v);
+            for (int r = 0; r < 16; r++) {
+                const uint32_t m = q * MEL_TILE + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m >= a.n_bins) continue;
+                float v = V[q][r];
+                if (a.scale == ZFLAC_MEL_LOG10) v = log10f(fmaxf(v, a.floor));
+                else if (a.scale == ZFLAC_MEL_LN) v = logf(fmaxf(v, a.floor));
+                const uint64_t at = LAYOUT == ZFLAC_MEL_BINS_FIRST ? (row * a.n_bins + m) * a.frames + j
+                                                                   : (row * a.frames + j) * a.n_bins + m;
+                dst[at] = conv_f32<DT>(v);
+                if constexpr (EX) mx = fmaxf(mx, v);
+            }
+    }
+    if constexpr (EX) {
+        // the row maximum: the wave's, then one atomic on the float's bits (signed max for the
+        // non-negative, unsigned min for the negative: the larger negative float has the smaller bits)
+        if (row_max) {
+#pragma unroll
+            for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+            const uint32_t u = __float_as_uint(mx);
+            if (lane == 0 && u != 0xFF800000u) {
+                if (u >> 31) atomicMin(reinterpret_cast<unsigned int*>(row_max + row), u);
+                else atomicMax(reinterpret_cast<int*>(row_max + row), (int)u);
+            }
         }
+    }
 }
 
-template <int DT, int LAYOUT>
-hipError_t launch_mt(uint32_t m_tiles, const MelArgs& a, uint32_t blocks, hipStream_t st) {
-    switch (m_tiles) {
-        case 1: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 1>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 2>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 4>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((k_mel<DT, LAYOUT, 8>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+template <int DT, int LAYOUT, int MT>
+__global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
+    mel_tile<DT, LAYOUT, MT, false>(a, nullptr, nullptr, 0);
+}
+
+template <int DT, int LAYOUT, int MT>
+__global__ __launch_bounds__(MEL_THREADS) void k_mel_ex(MelExArgs e) {
+    mel_tile<DT, LAYOUT, MT, true>(e.a, e.lengths, e.row_max, e.pad);
+}
+
+// k_mel_norm: (max(l, M_row - range) + add) * mul over the destination in place, every operation
+// one f32 rounding. A row's n_bins * frames elements are contiguous in either layout; a workgroup
+// pass takes MEL_NORM_CHUNK of them: elements up to the first 16-byte boundary one by one, then
+// 16-byte vectors, then the rest one by one (all one by one where dst is not element aligned).
+template <int DT>
+__device__ __forceinline__ typename Out<DT>::T mel_norm1(typename Out<DT>::T e, float thr, float add, float mul) {
+#pragma clang fp contract(off)
+    float l;
+    if constexpr (DT == ZFLAC_EXPORT_F32) l = e;
+    else if constexpr (DT == ZFLAC_EXPORT_F16) l = (float)e;
+    else l = __uint_as_float((uint32_t)e << 16);
+    const float c = fmaxf(l, thr);
+    const float s = c + add;
+    return conv_f32<DT>(s * mul);
 }
 
 template <int DT>
-hipError_t launch_dt(int layout, uint32_t m_tiles, const MelArgs& a, uint32_t blocks, hipStream_t st) {
-    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST>(m_tiles, a, blocks, st)
-                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST>(m_tiles, a, blocks, st);
+__global__ __launch_bounds__(MEL_NORM_THREADS) void k_mel_norm(MelNormArgs a) {
+    using OT = typename Out<DT>::T;
+    constexpr uint32_t ES = sizeof(OT), VEC = 16 / ES;
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t w = blockIdx.x; w < a.total; w += gridDim.x) {
+        const uint64_t row = w / a.chunks, start = (w - row * a.chunks) * MEL_NORM_CHUNK;
+        const uint32_t cnt = a.row_elems - start < MEL_NORM_CHUNK ? (uint32_t)(a.row_elems - start) : MEL_NORM_CHUNK;
+        float thr;
+        {
+#pragma clang fp contract(off)
+            thr = a.row_max[row] - a.range;
+        }
+        OT* const p = static_cast<OT*>(a.dst) + (row * a.row_elems + start);
+        const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
+        uint32_t head = cnt;
+        if (ad % ES == 0) {
+            head = (uint32_t)((16 - ad % 16) % 16) / ES;
+            if (head > cnt) head = cnt;
+        }
+        const uint32_t body = (cnt - head) / VEC, tail = cnt - head - body * VEC;
+        for (uint32_t i = tid; i < head; i += MEL_NORM_THREADS) p[i] = mel_norm1<DT>(p[i], thr, a.add, a.mul);
+        u32x4* const vp = reinterpret_cast<u32x4*>(p + head);
+        for (uint32_t v = tid; v < body; v += MEL_NORM_THREADS) {
+            u32x4 q = vp[v];
+            OT e[VEC];
+            __builtin_memcpy(e, &q, 16);
+#pragma unroll
+            for (uint32_t k = 0; k < VEC; k++) e[k] = mel_norm1<DT>(e[k], thr, a.add, a.mul);
+            __builtin_memcpy(&q, e, 16);
+            vp[v] = q;
+        }
+        OT* const tp = p + head + body * VEC;
+        for (uint32_t i = tid; i < tail; i += MEL_NORM_THREADS) tp[i] = mel_norm1<DT>(tp[i], thr, a.add, a.mul);
+    }
+}
+
+template <int DT, int LAYOUT, bool EX, typename A>
+hipError_t launch_mt(uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
+#define ZFLAC_MEL_LAUNCH(MT)                                                                              \
+    if constexpr (EX) hipLaunchKernelGGL((k_mel_ex<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); \
+    else hipLaunchKernelGGL((k_mel<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a);             \
+    break
+    switch (m_tiles) {
+        case 1: ZFLAC_MEL_LAUNCH(1);
+        case 2: ZFLAC_MEL_LAUNCH(2);
+        case 4: ZFLAC_MEL_LAUNCH(4);
+        case 8: ZFLAC_MEL_LAUNCH(8);
+        default: return hipErrorInvalidValue;
+    }
+#undef ZFLAC_MEL_LAUNCH
+    return hipGetLastError();
+}
+
+template <int DT, bool EX, typename A>
+hipError_t launch_dt(int layout, uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
+    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, EX>(m_tiles, a, blocks, st)
+                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, EX>(m_tiles, a, blocks, st);
+}
+
+template <bool EX, typename A>
+hipError_t launch_any(int dtype, int layout, uint32_t m_tiles, const A& a, uint64_t blocks, hipStream_t st) {
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    switch (dtype) {
+        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
+        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
+        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
 
 // rows * a.tiles workgroups (mel_plan_run keeps the product within gridDim.x's 2^31 - 1)
 hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st) {
-    const uint64_t blocks = rows * a.tiles;
-    if (blocks == 0) return hipSuccess;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    return launch_any<false>(dtype, layout, m_tiles, a, rows * a.tiles, st);
+}
+
+hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, const MelExArgs& e, uint64_t rows, hipStream_t st) {
+    return launch_any<true>(dtype, layout, m_tiles, e, rows * e.a.tiles, st);
+}
+
+// a.total passes of MEL_NORM_CHUNK elements, over at most 2^31 - 1 workgroups
+hipError_t launch_mel_norm(int dtype, const MelNormArgs& a, hipStream_t st) {
+    if (a.total == 0) return hipSuccess;
+    const uint32_t blocks = a.total < 0x7FFFFFFFull ? (uint32_t)a.total : 0x7FFFFFFFu;
     switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32>(layout, m_tiles, a, (uint32_t)blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16>(layout, m_tiles, a, (uint32_t)blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16>(layout, m_tiles, a, (uint32_t)blocks, st);
+        case ZFLAC_EXPORT_F32: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_F32>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
+        case ZFLAC_EXPORT_F16: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_F16>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
+        case ZFLAC_EXPORT_BF16: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_BF16>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
 }
 
 }  // namespace zflac

@@ -1,6 +1,6 @@
 // mel_host.cpp -- the feature plan (zflac_mel): its tables in device memory, its own stream, and
-// the launch of k_mel. A run stages nothing: the tables never change and the arguments go by
-// value, so runs of one plan on different streams may overlap.
+// the launches of k_mel, k_mel_ex and k_mel_norm. A run stages nothing: the tables never change
+// and the arguments go by value, so runs of one plan on different streams may overlap.
 #include "batch.h"
 #include "launch.h"
 #include "mel_plan.h"
@@ -41,6 +41,30 @@ int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) {
     });
 }
 
+// The launch arguments of a run the planner has accepted
+static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_frames, uint64_t row_stride,
+                        uint64_t first_frame, uint64_t frames, void* dst, const MelGrid& g) {
+    const MelPlan& p = m->plan;
+    MelArgs a;
+    a.wave = wave;
+    a.basis = m->basis.p;
+    a.filters = m->filters.p;
+    a.dst = dst;
+    a.wave_frames = wave_frames;
+    a.row_stride = row_stride;
+    a.first_frame = first_frame;
+    a.frames = frames;
+    a.tiles = g.tiles;
+    a.n_fft = p.n_fft;
+    a.hop = p.hop;
+    a.off = p.center ? p.n_fft / 2 : 0;
+    a.n_bins = p.n_bins;
+    a.bin_tiles = p.bin_tiles;
+    a.scale = p.scale;
+    a.floor = p.floor;
+    return a;
+}
+
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream) {
     MelGrid g;
@@ -50,25 +74,47 @@ int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames
     return guarded([&]() -> int {
         DeviceScope scope(m->device);
         const MelPlan& p = m->plan;
-        MelArgs a;
-        a.wave = wave;
-        a.basis = m->basis.p;
-        a.filters = m->filters.p;
-        a.dst = dst;
-        a.wave_frames = wave_frames;
-        a.row_stride = row_stride;
-        a.first_frame = first_frame;
-        a.frames = frames;
-        a.tiles = g.tiles;
-        a.n_fft = p.n_fft;
-        a.hop = p.hop;
-        a.off = p.center ? p.n_fft / 2 : 0;
-        a.n_bins = p.n_bins;
-        a.bin_tiles = p.bin_tiles;
-        a.scale = p.scale;
-        a.floor = p.floor;
+        const MelArgs a = mel_args(m, wave, wave_frames, row_stride, first_frame, frames, dst, g);
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
         ck(launch_mel(p.dtype, p.layout, p.m_tiles, a, rows, st));
+        if (!stream) ck(hipStreamSynchronize(st));
+        return E_OK;
+    });
+}
+
+// Up to three things on the one stream: row_max = -inf, k_mel (k_mel_ex unless the descriptor is
+// zflac_hip_mel_run's), k_mel_norm. Nothing is staged from the host.
+int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
+    MelGrid g;
+    const int rc = mel_plan_run_ex(m ? &m->plan : nullptr, r, g);
+    if (rc || g.blocks == 0) return rc;
+    return guarded([&]() -> int {
+        DeviceScope scope(m->device);
+        const MelPlan& p = m->plan;
+        MelExArgs e;
+        e.a = mel_args(m, r->wave_device, r->wave_frames, r->row_stride, r->first_frame, r->frames, r->dst_device, g);
+        e.lengths = r->lengths_device;
+        e.row_max = r->row_max_device;
+        e.pad = r->pad;
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
+        if (mel_run_is_plain(*r)) {
+            ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, r->rows, st));
+        } else {
+            if (e.row_max) ck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e.row_max), (int)0xFF800000u, r->rows, st));
+            ck(launch_mel_ex(p.dtype, p.layout, p.m_tiles, e, r->rows, st));
+        }
+        if (r->norm == ZFLAC_NORM_ROW_MAX) {
+            MelNormArgs n;
+            n.dst = r->dst_device;
+            n.row_max = r->row_max_device;
+            n.row_elems = (uint64_t)p.n_bins * r->frames;
+            n.chunks = (n.row_elems - 1) / MEL_NORM_CHUNK + 1;
+            n.total = r->rows * n.chunks;
+            n.range = r->range;
+            n.add = r->add;
+            n.mul = r->mul;
+            ck(launch_mel_norm(p.dtype, n, st));
+        }
         if (!stream) ck(hipStreamSynchronize(st));
         return E_OK;
     });

@@ -98,6 +98,38 @@ int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_
     return E_OK;
 }
 
+int mel_plan_run_ex(const MelPlan* p, const zflac_mel_run_desc* r, MelGrid& g) {
+    g = MelGrid{};
+    if (!p || !r) return E_INVALID_ARGUMENT;
+    if (r->size != sizeof(zflac_mel_run_desc)) return E_INVALID_ARGUMENT;
+    if (r->pad != ZFLAC_PAD_ZEROS && r->pad != ZFLAC_PAD_REFLECT) return E_INVALID_ARGUMENT;
+    if (r->norm != ZFLAC_NORM_NONE && r->norm != ZFLAC_NORM_ROW_MAX) return E_INVALID_ARGUMENT;
+    if (r->reserved != 0) return E_INVALID_ARGUMENT;
+    if (r->reserved2 != 0) return E_INVALID_ARGUMENT;
+    MelGrid shared;
+    const int rc = mel_plan_run(p, reinterpret_cast<uintptr_t>(r->wave_device), r->rows, r->wave_frames, r->row_stride,
+                                r->first_frame, r->frames, reinterpret_cast<uintptr_t>(r->dst_device), r->dst_bytes, shared);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(r->lengths_device) % sizeof(uint64_t)) return E_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(r->row_max_device) % sizeof(float)) return E_INVALID_ARGUMENT;
+    if (r->pad == ZFLAC_PAD_REFLECT && !p->center) return E_INVALID_ARGUMENT;
+    if (r->norm == ZFLAC_NORM_ROW_MAX) {
+        if (!r->row_max_device) return E_INVALID_ARGUMENT;
+        if (p->scale == ZFLAC_MEL_POWER) return E_INVALID_ARGUMENT;
+        if (!(std::isfinite(r->range) && r->range >= 0.0f)) return E_INVALID_ARGUMENT;
+        if (!std::isfinite(r->add)) return E_INVALID_ARGUMENT;
+        if (!(std::isfinite(r->mul) && r->mul != 0.0f)) return E_INVALID_ARGUMENT;
+    } else if (r->range != 0.0f || r->add != 0.0f || r->mul != 0.0f) {  // (a NaN is not 0)
+        return E_INVALID_ARGUMENT;
+    }
+    g = shared;
+    return E_OK;
+}
+
+bool mel_run_is_plain(const zflac_mel_run_desc& r) {
+    return r.pad == ZFLAC_PAD_ZEROS && r.norm == ZFLAC_NORM_NONE && !r.lengths_device && !r.row_max_device;
+}
+
 uint64_t mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center) {
     if (!hop) return 0;
     if (center) return n_samples ? n_samples / hop + 1 : 0;

@@ -70,6 +70,17 @@ struct MelGrid {
 int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
                  uint64_t first_frame, uint64_t frames, uintptr_t dst, size_t dst_bytes, MelGrid& g);
 
+// zflac_hip_mel_run_ex's checks, in this order: p (the plan, NULL = no plan) and r; size; pad, then
+// norm (known values); reserved, then reserved2; everything mel_plan_run checks, in its order, on
+// the fields of the same names (its arithmetic: this calls it); lengths_device's alignment (8);
+// row_max_device's alignment (4); ZFLAC_PAD_REFLECT with an uncentred plan; ZFLAC_NORM_ROW_MAX:
+// row_max_device, a log scale, range (finite, >= 0), add (finite), mul (finite, != 0);
+// ZFLAC_NORM_NONE: range, add, mul all 0. g is mel_plan_run's; rows == 0 is E_OK with
+// g.blocks == 0 once every check has passed (none of the added ones involves rows).
+int mel_plan_run_ex(const MelPlan* p, const zflac_mel_run_desc* r, MelGrid& g);
+// The descriptor that is zflac_hip_mel_run: zeros, no lengths, no row maximum, no normalisation
+bool mel_run_is_plain(const zflac_mel_run_desc& r);
+
 uint64_t mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center);
 
 }  // namespace zflac

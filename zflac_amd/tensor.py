@@ -2,7 +2,8 @@
 sample rate with sample_rate=: zflac_hip_batch_export_resampled, k_resample; with the channels
 mixed on the device with mix=: zflac_hip_batch_export_mixed / _export_resampled_mixed), and
 log-mel features of such a tensor in one more launch (MelSpectrogram, decode_to_features:
-zflac_hip_mel_run, k_mel).
+zflac_hip_mel_run, k_mel; with reflect padding, per-row lengths and the row-max clamp, Whisper's
+front end: zflac_hip_mel_run_ex, MelSpectrogram.whisper()).
 
     import torch                      # before zflac_amd loads its library (see below)
     from zflac_amd import Batch, tensor
@@ -313,6 +314,7 @@ def mel_filters(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="sl
 
 _MEL_SCALES = {"power": _lib.MEL_POWER, "log10": _lib.MEL_LOG10, "ln": _lib.MEL_LN}
 _MEL_LAYOUTS = {"bins_first": _lib.MEL_BINS_FIRST, "frames_first": _lib.MEL_FRAMES_FIRST}
+_MEL_PADS = {"zeros": _lib.PAD_ZEROS, "reflect": _lib.PAD_REFLECT}
 
 
 class MelSpectrogram:
@@ -320,19 +322,61 @@ class MelSpectrogram:
 
         mel = MelSpectrogram(16000)                     # n_fft 400, hop 160, 80 mel bins, log10
         feats, feat_lengths = mel(x, lengths)           # x: [B, T] or [B, C, T] float32 on cuda
+        mel = MelSpectrogram.whisper()                  # reflect padding and (max(x, M - 8) + 4) / 4
 
     window: "hann" (periodic, 0.5 - 0.5 cos(2 pi n / n_fft)) or n_fft values. filters: an array
     [n_bins, n_fft // 2 + 1], or None for mel_filters(sample_rate, n_fft, n_mels, **filter_kw).
     scale: "log10" or "ln" of max(v, floor), or "power" (the sums themselves; floor is not used).
-    center: frame t starts at sample t hop - n_fft / 2 (else at t hop); samples outside a row are
-    zero. There is no reflect padding: the first and last n_fft / (2 hop) frames differ from
-    torch.stft's default. The object owns a plan of the library: close() it, or use it in `with`."""
+    center: frame t starts at sample t hop - n_fft / 2 (else at t hop).
+
+    pad: "zeros" (the default): samples outside a row are zero, and there is no reflect padding:
+    the first and last n_fft / (2 hop) frames differ from torch.stft's default. "reflect" (needs
+    center=True; zflac_hip_mel_run_ex, ZFLAC_PAD_REFLECT): the row is reflected once about its
+    first and its last sample, which is torch.stft's pad_mode="reflect" and numpy.pad's "reflect".
+    reflect_at says where a row ends: "length" (the default) at its entry of `lengths`, so a
+    batch of rows of different lengths is reflected row by row and nothing past a row's length is
+    read; "end" at T, the end of the (zero-filled) tensor row, `lengths` then only giving
+    feature_lengths.
+    normalize: None, or (range, add, mul): every element becomes (max(x, M - range) + add) * mul
+    in f32, M the maximum of its row ([n_bins, frames] of one batch row and channel, as this call
+    computes them) before rounding to dtype; a log scale only. The maxima of the last call are
+    mel.last_row_max ([B] or [B, C] float32), or the third result with return_row_max=True.
+    With the defaults a call is one zflac_hip_mel_run, as before.
+    The object owns a plan of the library: close() it, or use it in `with`."""
+
+    @classmethod
+    def whisper(cls, n_mels=80, device=0, dtype=torch.float32):
+        """Whisper's front end: 16 kHz, n_fft 400, hop 160, the periodic Hann window, the Slaney
+        filterbank, log10 with floor 1e-10, reflect padding at the end of the row, and
+        (max(x, M - 8) + 4) / 4. Whisper's rows are 30 s (480,000 samples, zero-filled behind the
+        audio) and it drops the STFT's last frame: call the plan with frames=3000, which also
+        keeps that frame out of M. The result is the encoder's input [B, n_mels, 3000]."""
+        return cls(16000, 400, 160, n_mels, scale="log10", floor=1e-10, center=True, dtype=dtype, device=device,
+                   pad="reflect", normalize=(8.0, 4.0, 0.25), reflect_at="end")
 
     def __init__(self, sample_rate, n_fft=400, hop=160, n_mels=80, window="hann", filters=None, scale="log10",
-                 floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, **filter_kw):
+                 floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, pad="zeros",
+                 normalize=None, reflect_at="length", **filter_kw):
+        import math
+
         import numpy as np
 
         check_single_runtime()
+        if pad not in _MEL_PADS:
+            raise ValueError("pad is 'zeros' or 'reflect'")
+        if pad == "reflect" and not center:
+            raise ValueError("pad='reflect' needs center=True")
+        if reflect_at not in ("length", "end"):
+            raise ValueError("reflect_at is 'length' or 'end'")
+        if normalize is not None:
+            normalize = tuple(float(v) for v in normalize)
+            if len(normalize) != 3 or not all(math.isfinite(v) for v in normalize) or normalize[0] < 0 or normalize[2] == 0:
+                raise ValueError("normalize is (range >= 0, add, mul != 0), all finite")
+            if scale == "power":
+                raise ValueError("normalize needs a log scale")
+        self.pad, self.normalize, self.reflect_at = pad, normalize, reflect_at
+        self.last_row_max = None
+        self._keep = None
         if dtype not in _DTYPES or dtype == torch.int32:
             raise TypeError("dtype is float32, float16 or bfloat16")
         if scale not in _MEL_SCALES:
@@ -381,13 +425,14 @@ class MelSpectrogram:
             return torch.where(n >= self.n_fft, (n - self.n_fft) // self.hop + 1, torch.zeros_like(n))
         return int(self._L.zflac_hip_mel_frames(int(n_samples), self.n_fft, self.hop, int(self.center)))
 
-    def __call__(self, x, lengths=None, frames=None, first_frame=0, out=None, stream=None):
+    def __call__(self, x, lengths=None, frames=None, first_frame=0, out=None, stream=None, return_row_max=False):
         """x: contiguous float32 [B, T] or [B, C, T] on cuda:<device>; lengths: valid samples per
         batch row (default T) -> (features, feature_lengths). features: [B, (C,) n_bins, frames]
         (layout="bins_first") or [B, (C,) frames, n_bins], frame j of it being feature frame
         first_frame + j; frames defaults to mel_frames(T) - first_frame. feature_lengths: int64
         [B], clamp(mel_frames(lengths) - first_frame, 0, frames). Enqueued on `stream` (default:
-        torch's current stream of the device); nothing is synchronised."""
+        torch's current stream of the device); nothing is synchronised. return_row_max=True:
+        -> (features, feature_lengths, row_max), row_max float32 [B] or [B, C] (see the class)."""
         check_single_runtime()
         if self._h is None:
             raise ValueError("the plan is closed")
@@ -428,16 +473,35 @@ class MelSpectrogram:
         rows = 1
         for n in lead:
             rows *= int(n)
+        ex = self.pad != "zeros" or self.normalize is not None or return_row_max
+        row_max = torch.empty(lead, dtype=torch.float32, device=dev) if ex else None
+        self.last_row_max = row_max
         if rows == 0:
-            return out, feature_lengths
+            return (out, feature_lengths, row_max) if return_row_max else (out, feature_lengths)
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         if not stream.cuda_stream:
             stream.synchronize()  # the null stream has no handle: the plan's own stream, complete on return
-        rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, out.data_ptr(),
-                                       out.numel() * out.element_size(), stream.cuda_stream or None)
-        errors.check(rc, "mel_run")
-        return out, feature_lengths
+        if not ex:
+            rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, out.data_ptr(),
+                                           out.numel() * out.element_size(), stream.cuda_stream or None)
+            errors.check(rc, "mel_run")
+            return out, feature_lengths
+        per_row = None
+        if self.reflect_at == "length":  # one length per row of the launch: [B, C, T] has C rows per entry
+            per_row = lengths.clamp(min=0).repeat_interleave(rows // int(x.shape[0])).contiguous()
+        rng, add, mul = self.normalize or (0.0, 0.0, 0.0)
+        d = _lib.zflac_mel_run_desc(ctypes.sizeof(_lib.zflac_mel_run_desc), _MEL_PADS[self.pad],
+                                    _lib.NORM_NONE if self.normalize is None else _lib.NORM_ROW_MAX, 0, x.data_ptr(), rows,
+                                    T, T, None if per_row is None else per_row.data_ptr(), first_frame, frames,
+                                    out.data_ptr(), out.numel() * out.element_size(), row_max.data_ptr(), rng, add, mul, 0)
+        rc = self._L.zflac_hip_mel_run_ex(self._h, ctypes.byref(d), stream.cuda_stream or None)
+        errors.check(rc, "mel_run_ex")
+        self._keep = per_row  # read by the launch: alive until the next call, and not reused before `stream` is past it
+        for t in (per_row, row_max):
+            if t is not None and stream.cuda_stream:
+                t.record_stream(stream)
+        return (out, feature_lengths, row_max) if return_row_max else (out, feature_lengths)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
