@@ -180,7 +180,10 @@ int zflac_hip_batch_read(zflac_batch* b, size_t i, void* out, size_t out_bytes, 
     return guarded([&]() -> int {
         ck(hipSetDevice(b->device));
         // a device verdict stands in for the host hash (a mismatch is already s.err)
-        return read_samples(b, s, out, verify_md5 && !s.md5_dev);  // InvalidChecksum at :279-280
+        int rc = read_samples(b, s, out, verify_md5 && !s.md5_dev);  // InvalidChecksum at :279-280
+        // (a left-justified stream: the verdict belongs to the samples before the shift)
+        if (rc == E_INVALID_CHECKSUM && md5_before_justify(b, s)) rc = E_OK;
+        return rc;
     });
 }
 

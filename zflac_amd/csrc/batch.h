@@ -219,6 +219,12 @@ void hub_flush(Md5Hub& h);           // one launch over every pending run (calle
 void hub_release(zflac_batch* b);    // flush a run still pending in its device's md5 hub
 void hub_forget(zflac_batch* b);     // drop a run from its device's md5 hub without hashing it
 int read_samples(zflac_batch* b, StreamState& s, void* out, bool hash);
+// Internal batch flag (never set by a caller of the ABI): the kernels store the samples without
+// the left-justify shift. Only md5_before_justify creates such a batch.
+constexpr int FLAG_NO_JUSTIFY = 1 << 30;
+// After a digest mismatch of a left-justified stream: is the digest of its samples before the
+// shift STREAMINFO's, as zflac hashes them (src/zflac.zig:267-306)?
+bool md5_before_justify(zflac_batch* b, StreamState& s);
 void plan_md5_pipeline(zflac_batch* b);
 void finish_md5(zflac_batch* b, bool timing);
 

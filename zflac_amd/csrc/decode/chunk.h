@@ -364,6 +364,11 @@ __device__ __forceinline__ void fast_chunk(LaneCtx& L, Rdr& rd, Pred<KIND, M>& p
     uint32_t lim = NC == 1 ? 0xFFFFFFFFu : 0u;
     int32_t vmax = 0, vmin = 0;  // range of the chunk's samples (8/16-bit containers)
     bool v32 = false;            // 32-bit containers: a sum outside i32
+    // 32-bit containers, stereo, not WIDE: bit 31 set once a sample entering the decorrelation
+    // lies outside [-2^30, 2^30): a predicted sample may leave the stream's depth (zflac keeps
+    // whatever fits the SampleType), and then the wrapping i32 decorrelation below is no longer
+    // known to be exact. Such a chunk goes back to the generic path and its per-sample checks.
+    uint32_t big = 0;
     // packed output of 8 samples: stored at once, except the chunk's last group, which stays
     // pending until after the next chunk-start wait (a store issued just before that wait
     // would expose its whole latency)
@@ -441,6 +446,7 @@ __device__ __forceinline__ void fast_chunk(LaneCtx& L, Rdr& rd, Pred<KIND, M>& p
             int32_t o = (int32_t)((uint32_t)s << wasted);
             if constexpr (LAY == LAY_STEREO) {
                 int32_t x0, x1;
+                if constexpr (!wide) big |= (uint32_t)o ^ ((uint32_t)o << 1);
                 pair_values(o, x0, x1);
                 o = decorrelate<DECOR>(L.chan_code, c1m, x0, x1);
                 if (wide) ovf |= decor_overflows<KIND>(L.chan_code, c, x0, x1) ? 1u : 0u;
@@ -554,6 +560,7 @@ __device__ __forceinline__ void fast_chunk(LaneCtx& L, Rdr& rd, Pred<KIND, M>& p
     const bool dry = rd.dry();  // the ring ran out of stored words: stale reads, redo the chunk
     if constexpr (NC == 1) bad |= lim < L.thr || dry || (MIXED && vrange);
     else bad |= lim > 32u || dry;
+    if constexpr (KIND == 2 && LAY == LAY_STEREO && !WIDE) bad |= (int32_t)big < 0 && L.chan_code >= 8;
     if constexpr (KIND == 2) vbad = v32;
     else vbad = vmax > (1 << (Kind<KIND>::SB - 1)) - 1 || vmin < -(1 << (Kind<KIND>::SB - 1));
 }

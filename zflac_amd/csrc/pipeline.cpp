@@ -157,7 +157,7 @@ void alloc_class(zflac_batch* b, Class& C, const zflac_stream* src) {
         D.nch = (uint8_t)s.nch;
         D.dcode = (uint8_t)s.first.dcode;
         D.si_bps = (uint8_t)s.si.bps;
-        D.justify = justify_of(s.si.bps);
+        D.justify = (b->flags & FLAG_NO_JUSTIFY) ? 0 : justify_of(s.si.bps);
         D.first_chunk = (uint32_t)C.chunks.size();
         const uint64_t abase0 = D.in_begin & ~(uint64_t)15;
         for (uint64_t a = abase0; a < D.in_end; a += CHUNK_BYTES) {
