@@ -206,6 +206,37 @@ int zflac_hip_batch_decode_buckets(zflac_batch *b, uint32_t *used, uint32_t *pla
 #define ZFLAC_FRONT_SCAN 1
 #define ZFLAC_FRONT_HOP 2
 int zflac_hip_batch_front(zflac_batch *b, int *planned, int *used);
+/* Where stream i's digest (zflac_hip_batch_md5) came from in the last completed run of a
+ * ZFLAC_FLAG_DEVICE_MD5 batch:
+ *   _NONE          no digest: the stream ended in an error (InvalidChecksum included), or the batch
+ *                  has no device MD5;
+ *   _PIPELINED     the hash _submit enqueued behind the decode, in the device's md5 hub or (with
+ *                  ZFLAC_MD5_NOHUB) on the run stream: the streams the parallel pass certified;
+ *   _SYNC          the synchronous hash launch of _wait: streams the sequential planner finished,
+ *                  or a class that was run again;
+ *   _HOST_RECHECK  the device digest of a left-justified stream (9..15, 17..31 bits) was not
+ *                  STREAMINFO's; the stream was decoded again alone, without the shift, hashed on
+ *                  the host, and that digest matched (zflac hashes before it left-justifies and keeps
+ *                  samples beyond the stream's depth). _md5 then returns STREAMINFO's digest.
+ * ZFLAC_E_INVALID_ARGUMENT: a NULL batch or pointer, before the first completed run, i out of range. */
+#define ZFLAC_MD5_SRC_NONE 0
+#define ZFLAC_MD5_SRC_PIPELINED 1
+#define ZFLAC_MD5_SRC_SYNC 2
+#define ZFLAC_MD5_SRC_HOST_RECHECK 3
+int zflac_hip_batch_md5_source(zflac_batch *b, size_t i, int *source);
+/* *kernels: the OR of the ZFLAC_MD5_K_* of the hash launches the last completed run's device
+ * digests came from (_PIPELINED and _SYNC streams; a hub launch counts for every run it hashed):
+ * k_md5_coop (every job of the launch in one form, cooperative loads through LDS), k_md5_multi
+ * (jobs of several forms in one hub launch; also what a k_md5_coop launch falls back to where the
+ * device refuses its LDS), k_md5 (a single run's jobs, each lane its own loads). 0 without
+ * ZFLAC_FLAG_DEVICE_MD5. *rechecks: over the batch's lifetime, how often a left-justified stream
+ * was decoded again to take its digest before the shift, after a mismatch in _wait (see
+ * _HOST_RECHECK) or in _batch_read's host hash; a stream inside its depth whose STREAMINFO MD5 is
+ * right never counts. ZFLAC_E_INVALID_ARGUMENT as for _decode_buckets. */
+#define ZFLAC_MD5_K_COOP 1u
+#define ZFLAC_MD5_K_MULTI 2u
+#define ZFLAC_MD5_K_LANE 4u
+int zflac_hip_batch_md5_stats(zflac_batch *b, uint32_t *kernels, uint64_t *rechecks);
 size_t zflac_hip_batch_size(zflac_batch *b);
 void zflac_hip_batch_destroy(zflac_batch *b);
 
@@ -544,7 +575,8 @@ const char *zflac_hip_build_id(void);
  *    ZFLAC_MIX_MAX_CHANNELS, zflac_hip_batch_export_mixed, zflac_hip_batch_export_resampled_mixed;
  *    zflac_mel_desc, zflac_mel, ZFLAC_MEL_*, zflac_hip_mel_create, zflac_hip_mel_run,
  *    zflac_hip_mel_frames, zflac_hip_mel_destroy; zflac_mel_run_desc, zflac_hip_mel_run_ex,
- *    ZFLAC_PAD_*, ZFLAC_NORM_*. */
+ *    ZFLAC_PAD_*, ZFLAC_NORM_*; zflac_hip_batch_md5_source, ZFLAC_MD5_SRC_*,
+ *    zflac_hip_batch_md5_stats, ZFLAC_MD5_K_*. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -10,7 +10,7 @@ import pytest
 import oracle
 import synth
 import zflac_amd
-from zflac_amd import errors
+from zflac_amd import _lib, errors
 
 from . import malformed
 from .util import GOLDEN, PARITY_CONFIGS, expected_samples, load_fixture_manifest, load_kats, splice_frames
@@ -119,6 +119,31 @@ def _streaminfo_md5(flac: bytes) -> bytes:
     return flac[26:42]  # 'fLaC', block header, then STREAMINFO bytes 18..33
 
 
+def _justified(flac: bytes) -> bool:
+    """STREAMINFO's depth is one zflac left-justifies (9..15, 17..31 bits)."""
+    bps = (((flac[20] & 1) << 4) | (flac[21] >> 4)) + 1
+    return 9 <= bps <= 15 or 17 <= bps <= 31
+
+
+def _assert_device_digests(b, datas, ok, runs: int = 1):
+    """The digests of the streams `ok` are the hash kernels' own (zflac_hip_batch_md5_source: the
+    pipelined or the synchronous launch, never md5_before_justify's second decode, after which
+    _md5 returns STREAMINFO's digest whatever the kernel computed). Over `runs` runs of the batch
+    only its streams that really fail their checksum, of a left-justified depth, were decoded
+    again. Returns (streams hashed by the synchronous launch, kernels)."""
+    src = {i: b.md5_source(i) for i in ok}
+    assert all(s in (_lib.MD5_SRC_PIPELINED, _lib.MD5_SRC_SYNC) for s in src.values()), src
+    refused = [i for i in range(len(datas)) if errors.NAMES.get(b.info(i)[0]) == "InvalidChecksum"]
+    assert all(b.md5_source(i) == _lib.MD5_SRC_NONE for i in range(len(datas)) if i not in ok)
+    kernels, rechecks = b.md5_stats()
+    assert rechecks == runs * sum(_justified(datas[i]) for i in refused), (rechecks, runs, refused)
+    assert kernels and not kernels & ~(_lib.MD5_K_COOP | _lib.MD5_K_MULTI | _lib.MD5_K_LANE), kernels
+    n_sync = sum(s == _lib.MD5_SRC_SYNC for s in src.values())
+    t = b.timings()
+    assert n_sync <= t.sequential_streams or t.rest_launches, (n_sync, t.sequential_streams, t.rest_launches)
+    return n_sync, kernels
+
+
 def test_device_md5_every_class(gpu_ready):
     """k_md5 (ZFLAC_FLAG_DEVICE_MD5): every container/depth class (8..32-bit, justify
     undone, 24-bit as 3 bytes), ragged lengths and unaligned stream bases in one batch;
@@ -129,12 +154,14 @@ def test_device_md5_every_class(gpu_ready):
     datas = [s.flac for s in streams] + [_CASES["wrong_md5"][0]]
     b = zflac_amd.Batch(datas, device_md5=True, timing=True)
     b.run()
+    ok = []
     for i, data in enumerate(datas):
         r = oracle.decode(data)
         rc, _ = b.info(i)
         assert errors.NAMES.get(rc) == r.error, (i, rc, r.error)
         if r.error != "OK":
             continue
+        ok.append(i)
         dig = b.md5(i)
         assert dig is not None, i
         assert dig == _streaminfo_md5(data), i
@@ -142,6 +169,9 @@ def test_device_md5_every_class(gpu_ready):
         d = b.read(i)  # device verdict stands in for the host hash
         np.testing.assert_array_equal(d.samples.values, r.samples)
     assert b.timings().md5_ms > 0
+    # several forms in one batch: the hub's launch is k_md5_multi; no digest needed a second decode
+    _, kernels = _assert_device_digests(b, datas, ok)
+    assert kernels & _lib.MD5_K_MULTI, kernels
     b.close()
 
 
@@ -150,8 +180,8 @@ def test_device_md5_every_class(gpu_ready):
                                   "c4_24bit_lpc32_wasted", "stereo32", "stereo31_ls_loud"])
 def test_device_md5_cooperative_loads(gpu_ready, name, loads):
     """One class per batch (every job in one mode: k_md5_coop, the wave's 64 streams read
-    through LDS; ZFLAC_MD5_LANE_LOADS=1 forces k_md5). 70 streams (a second, partial wave
-    whose idle lanes only help load) of ragged lengths (lanes leave the unit loop at
+    through LDS; ZFLAC_MD5_LANE_LOADS=1 at creation forces lane loads on the pipelined hash:
+    k_md5_multi in the hub). 70 streams (a second, partial wave whose idle lanes only help load) of ragged lengths (lanes leave the unit loop at
     different units); one stream's MD5 corrupted. Digests equal STREAMINFO and hashlib."""
     cfg = PARITY_CONFIGS[name]
     bs = cfg["block_size"]
@@ -166,7 +196,7 @@ def test_device_md5_cooperative_loads(gpu_ready, name, loads):
         b = zflac_amd.Batch(datas, device_md5=True, timing=True)
     finally:
         os.environ.pop("ZFLAC_MD5_LANE_LOADS", None)
-    for _ in range(2):  # the second run reuses the batch (and the md5 hub)
+    for run in range(2):  # the second run reuses the batch (and the md5 hub)
         b.run()
         for i, data in enumerate(datas):
             rc, _ = b.info(i)
@@ -175,6 +205,18 @@ def test_device_md5_cooperative_loads(gpu_ready, name, loads):
                 continue
             assert rc == 0, (i, rc)
             assert b.md5(i) == _streaminfo_md5(data), i
+        # the digests are the kernel's own; stream 65 alone was decoded again, if its depth is justified
+        n_sync, kernels = _assert_device_digests(b, datas, [i for i in range(70) if i != 65], runs=run + 1)
+        print(f"{name}-{loads} run {run}: {n_sync} of 69 digests from the synchronous launch, kernels {kernels:#x}")
+        # (a first run that met a decode bucket outside its plan hashes its class after the `rest`
+        # launch, synchronously; the second run has every launch it needs and the pipelined hash)
+        assert n_sync < 69 or (run == 0 and b.timings().rest_launches), (run, n_sync)
+        if n_sync == 69:
+            continue
+        if loads == "lane":
+            assert kernels & _lib.MD5_K_MULTI, kernels
+        else:  # (k_md5_multi alone: the device refused k_md5_coop's LDS)
+            assert kernels & _lib.MD5_K_COOP or kernels == _lib.MD5_K_MULTI, kernels
     r = oracle.decode(datas[3])
     assert b.md5(3) == _md5_pre_justify(r.samples, r.bits_per_sample)
     b.close()
@@ -501,6 +543,7 @@ def test_pipelined_device_md5_overlapped(gpu_ready):
         for b in bs:
             b.wait()
         for g, b in zip(groups, bs):
+            ok = []
             for i, data in enumerate(g):
                 if data not in refs:
                     refs[data] = oracle.decode(data, "fast")
@@ -509,8 +552,11 @@ def test_pipelined_device_md5_overlapped(gpu_ready):
                 assert errors.NAMES.get(rc) == r.error, (rnd, i)
                 if r.error != "OK":
                     continue
+                ok.append(i)
                 assert b.md5(i) == _streaminfo_md5(data), (rnd, i)
                 assert b.md5(i) == _md5_pre_justify(r.samples, r.bits_per_sample), (rnd, i)
+            # (wrong_md5 is a 16-bit stream: no recheck in any batch)
+            _assert_device_digests(b, g, ok, runs=rnd + 1)
         assert bs[0].timings().md5_ms > 0
     for b in bs:
         b.close()

@@ -17,7 +17,7 @@ import pytest
 
 import oracle
 import zflac_amd
-from zflac_amd import errors
+from zflac_amd import _lib, errors
 
 from . import craft, value_edges
 
@@ -133,10 +133,28 @@ def _read(b, i):
         return type(e).__name__, None, None
 
 
+def _needs_recheck(c) -> bool:
+    """The device digest of this stream cannot be STREAMINFO's: a left-justified depth, and either
+    a stream that really fails its checksum, or an OK stream with a sample beyond its depth, of
+    which the shift has pushed out bits that zflac hashed: the hashed bytes ((bps + 7) / 8 of
+    them) of the sample and of the sample shifted left and back differ. A 24-bit sample never
+    does that (its three hashed bytes survive the shift by eight). md5_before_justify decodes
+    exactly these streams again."""
+    bps = c.cr.bps
+    js = 16 - bps if 9 <= bps <= 15 else 32 - bps if 17 <= bps <= 31 else 0
+    if not js:
+        return False
+    if c.error != "OK":
+        return c.error == "InvalidChecksum"
+    kept, hashed = craft.widths(bps)[0] - js, 8 * ((bps + 7) // 8)
+    return any((value_edges.wrap(v, kept) ^ v) & ((1 << hashed) - 1) for v in c.cr.pcm)
+
+
 def _verdicts(name, walk, device_md5):
     """Decode the family's batch twice; every disagreement of both runs, as printable rows."""
     cases, refs = value_edges.batch(name), _refs(name)
     refused = sum(c.error != "OK" for c in cases)
+    rechecked = sum(_needs_recheck(c) for c in cases)
     b = zflac_amd.Batch([c.data for c in cases], timing=True, device_md5=device_md5, walk=walk)
     bad = []
     try:
@@ -159,6 +177,16 @@ def _verdicts(name, walk, device_md5):
                     bad.append((run, c.name, "differs from the writer's PCM"))
                 elif md5 != c.cr.md5:
                     bad.append((run, c.name, "device digest"))
+                elif device_md5:
+                    # the digest is the hash kernel's own, but for the streams beyond their depth
+                    src = b.md5_source(i)
+                    want = (_lib.MD5_SRC_HOST_RECHECK,) if _needs_recheck(c) else (_lib.MD5_SRC_PIPELINED, _lib.MD5_SRC_SYNC)
+                    if src not in want:
+                        bad.append((run, c.name, "digest source", src, want))
+            if device_md5 and b.md5_stats().rechecks != (run + 1) * rechecked:
+                bad.append((run, "rechecks", b.md5_stats().rechecks, "expected", (run + 1) * rechecked))
+            if not device_md5 and b.md5_stats() != (0, 0):
+                bad.append((run, "md5 stats without the device MD5", b.md5_stats()))
             if b.timings().sequential_streams != refused:
                 bad.append((run, "sequential streams", b.timings().sequential_streams, "refused streams", refused))
     finally:
@@ -179,7 +207,12 @@ def test_family_verdicts(gpu_ready, name, walk):
     The twelve OK streams of depth 12 and 20 in family S whose edge sample lies beyond the depth
     but inside the container are the ones whose digest cannot be taken from the left-justified
     samples (a 12-bit sample of 32767 has lost its top four bits there): md5_before_justify
-    (md5_host.cpp) answers for them."""
+    (md5_host.cpp) answers for them. zflac_hip_batch_md5_source says HOST_RECHECK for exactly the
+    streams of that kind (_needs_recheck, from the family list) and the pipelined or synchronous
+    hash launch for every other OK stream; zflac_hip_batch_md5_stats counts one recheck per such
+    stream and run, and none else."""
+    s12 = [c for c in value_edges.batch("S") if _needs_recheck(c)]
+    assert len(s12) == 12 and all(c.cr.bps in (12, 20) and c.error == "OK" for c in s12)
     bad = _verdicts(name, walk, device_md5=True)
     assert not bad, (walk, bad[:8], len(bad))
 

@@ -112,6 +112,9 @@ SIGNATURES = {
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "zflac_hip_batch_md5_source": (ctypes.c_int, [_P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
+    "zflac_hip_batch_md5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
+                                                 ctypes.POINTER(ctypes.c_uint64)]),
     "zflac_hip_batch_size": (ctypes.c_size_t, [_P]),
     "zflac_hip_batch_destroy": (None, [_P]),
     "zflac_hip_error_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -159,6 +162,15 @@ BUCKET_ALL = 127
 # zflac_hip_batch_front: what built the frame table (ZFLAC_FRONT_*), ORed over the batch's classes
 FRONT_SCAN = 1
 FRONT_HOP = 2
+# zflac_hip_batch_md5_source: where a stream's digest came from (ZFLAC_MD5_SRC_*)
+MD5_SRC_NONE = 0
+MD5_SRC_PIPELINED = 1
+MD5_SRC_SYNC = 2
+MD5_SRC_HOST_RECHECK = 3
+# zflac_hip_batch_md5_stats: one bit per hash kernel (ZFLAC_MD5_K_*)
+MD5_K_COOP = 1
+MD5_K_MULTI = 2
+MD5_K_LANE = 4
 
 _lib = None
 

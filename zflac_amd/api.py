@@ -5,6 +5,7 @@ Here: decode(reader) -> DecodedFLAC, raising zflac-named errors.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import dataclasses
 
@@ -52,6 +53,9 @@ class DecodedFLAC:
 
     def deinit(self, allocator=None) -> None:  # parity with DecodedFLAC.deinit
         self.samples = Samples(self.samples.tag, self.samples.values[:0])
+
+
+Md5Stats = collections.namedtuple("Md5Stats", "kernels rechecks")  # of Batch.md5_stats()
 
 
 def _read_all(reader) -> bytes:
@@ -198,6 +202,23 @@ class Batch:
         planned, used = ctypes.c_int(), ctypes.c_int()
         errors.check(self._L.zflac_hip_batch_front(self._h, ctypes.byref(planned), ctypes.byref(used)), "batch_front")
         return planned.value, used.value
+
+    def md5_source(self, i: int) -> int:
+        """Where stream i's digest came from in the last completed run (zflac_hip_batch_md5_source):
+        _lib.MD5_SRC_NONE, _PIPELINED, _SYNC or _HOST_RECHECK."""
+        src = ctypes.c_int()
+        errors.check(self._L.zflac_hip_batch_md5_source(self._h, i, ctypes.byref(src)), "batch_md5_source")
+        return src.value
+
+    def md5_stats(self):
+        """(kernels, rechecks) (zflac_hip_batch_md5_stats), as attributes of the result too: the
+        _lib.MD5_K_* of the hash launches the last completed run's digests came from, and how
+        often, over the batch's lifetime, a left-justified stream was decoded again to take its
+        digest before the shift."""
+        kernels, rechecks = ctypes.c_uint32(), ctypes.c_uint64()
+        errors.check(self._L.zflac_hip_batch_md5_stats(self._h, ctypes.byref(kernels), ctypes.byref(rechecks)),
+                     "batch_md5_stats")
+        return Md5Stats(kernels.value, rechecks.value)
 
     def device_samples(self, i: int) -> int:
         return self._L.zflac_hip_batch_device_samples(self._h, i) or 0

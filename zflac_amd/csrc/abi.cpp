@@ -282,6 +282,23 @@ int zflac_hip_batch_front(zflac_batch* b, int* planned, int* used) {
     return E_OK;
 }
 
+static_assert(ZFLAC_MD5_K_COOP == MD5_K_COOP && ZFLAC_MD5_K_MULTI == MD5_K_MULTI && ZFLAC_MD5_K_LANE == MD5_K_LANE,
+              "ZFLAC_MD5_K_* (zflac_hip.h) and Md5Kernel (common.h) disagree");
+
+int zflac_hip_batch_md5_source(zflac_batch* b, size_t i, int* source) {
+    if (!b || !b->ran || i >= b->streams.size() || !source) return E_INVALID_ARGUMENT;
+    const StreamState& s = b->streams[i];
+    *source = (s.err || !s.md5_dev) ? ZFLAC_MD5_SRC_NONE : s.md5_src;
+    return E_OK;
+}
+
+int zflac_hip_batch_md5_stats(zflac_batch* b, uint32_t* kernels, uint64_t* rechecks) {
+    if (!b || !kernels || !rechecks || !b->ran || b->submitted) return E_INVALID_ARGUMENT;
+    *kernels = b->md5_kernels;
+    *rechecks = b->md5_rechecks;
+    return E_OK;
+}
+
 int zflac_hip_batch_export_ms(zflac_batch* b, double* ms) {
     if (!b || !ms || b->export_ms < 0) return E_INVALID_ARGUMENT;
     *ms = b->export_ms;

@@ -86,6 +86,7 @@ struct StreamState : StreamPlan {  // the host parse (stream_plan.h), then:
     const void* dev_samples = nullptr;  // device pointer of the decoded samples
     int md5_dev = 0;                    // 0 not hashed on the device, 1 match, 2 mismatch
     uint8_t md5_dig[16] = {};           // device digest (md5_dev != 0)
+    int md5_src = 0;                    // ZFLAC_MD5_SRC_* of md5_dig (zflac_hip_batch_md5_source)
     std::unique_ptr<DevBuf<uint8_t>> override_out;
 };
 
@@ -336,5 +337,11 @@ struct zflac_batch {
     // zflac_hip_batch_front: over the classes, the fronts the last completed run was enqueued
     // with and the ones its frame tables came from (ZFLAC_FRONT_*)
     int front_planned = 0, front_used = 0;
+    // zflac_hip_batch_md5_stats: the Md5Kernel of the pipelined launch that holds the run in flight
+    // (set by submit on the run stream, or by the hub's flush under the hub's lock, before
+    // md5_pending falls), the kernels the last completed run's digests came from, and the stream
+    // decodes of md5_before_justify over the batch's lifetime
+    uint32_t md5_pipe_kernel = 0, md5_kernels = 0;
+    uint64_t md5_rechecks = 0;
     ~zflac_batch();  // abi.cpp
 };

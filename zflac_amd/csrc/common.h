@@ -233,6 +233,14 @@ struct Md5Job {
                              // this run (the sequential planner decodes it later), no hash
 };
 
+// The hash kernel a launch took (launch_md5, launch_md5_multi), as zflac_hip_batch_md5_stats
+// reports it: ZFLAC_MD5_K_* of zflac_hip.h.
+enum Md5Kernel : uint32_t {
+    MD5_K_COOP = 1,   // k_md5_coop<MODE>
+    MD5_K_MULTI = 2,  // k_md5_multi
+    MD5_K_LANE = 4,   // k_md5
+};
+
 // Jobs of several runs for one k_md5_multi launch (the md5 hub, md5_host.cpp): segment s is
 // jobs[s][0 .. start[s+1] - start[s]), its digests go to dig[s].
 constexpr int MD5_MAX_SEGS = 16;

@@ -40,9 +40,11 @@ hipError_t launch_walk_wave(int kind, const DecodeArgs& a, uint32_t max_frames, 
 hipError_t launch_crc16(const Crc16Args& a, uint32_t max_frames, hipStream_t st);
 
 // md5.hip. coop_mode: the Md5Mode every job shares with 16-byte aligned samples (the
-// cooperative-load kernel), or -1 (lane-per-stream loads)
-hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode);
-hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode);
+// cooperative-load kernel), or -1 (lane-per-stream loads). *kernel (optional): the Md5Kernel
+// launched, k_md5_multi where the device refuses k_md5_coop's LDS; 0 when there was no job.
+hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode,
+                      uint32_t* kernel = nullptr);
+hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode, uint32_t* kernel = nullptr);
 
 // export.hip
 hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st);

@@ -447,8 +447,9 @@ uint32_t md5_wg_waves_dev() {
 }
 
 template <int MODE>
-hipError_t launch_coop(const Md5Segs& sg, uint32_t n, hipStream_t st) {
+hipError_t launch_coop(const Md5Segs& sg, uint32_t n, hipStream_t st, uint32_t* kernel) {
     const uint32_t w = md5_wg_waves_dev();
+    *kernel = MD5_K_MULTI;  // (until the cooperative launch below)
     if (w == 0) {  // no room for a tile: the lane-load kernel
         hipLaunchKernelGGL(k_md5_multi, dim3((n + 63) / 64), dim3(64), 0, st, sg);
         return hipGetLastError();
@@ -459,23 +460,32 @@ hipError_t launch_coop(const Md5Segs& sg, uint32_t n, hipStream_t st) {
         hipLaunchKernelGGL(k_md5_multi, dim3((n + 63) / 64), dim3(64), 0, st, sg);
         return hipGetLastError();
     }
+    *kernel = MD5_K_COOP;
     hipLaunchKernelGGL(k_md5_coop<MODE>, dim3((n + 64 * w - 1) / (64 * w)), dim3(64 * w), lds, st, sg);
     return hipGetLastError();
 }
 
-hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode) {
+hipError_t launch_md5_multi(const Md5Segs& sg, hipStream_t st, int coop_mode, uint32_t* kernel) {
+    uint32_t none = 0;
+    if (!kernel) kernel = &none;
+    *kernel = 0;
     const uint32_t n = sg.start[sg.nseg];
     if (!n) return hipSuccess;
     switch (coop_mode) {
-        case MD5_RAW: return launch_coop<MD5_RAW>(sg, n, st);
-        case MD5_S16_SHIFT: return launch_coop<MD5_S16_SHIFT>(sg, n, st);
-        case MD5_S32_SHIFT: return launch_coop<MD5_S32_SHIFT>(sg, n, st);
-        case MD5_S24: return launch_coop<MD5_S24>(sg, n, st);
-        default: hipLaunchKernelGGL(k_md5_multi, dim3((n + 63) / 64), dim3(64), 0, st, sg); return hipGetLastError();
+        case MD5_RAW: return launch_coop<MD5_RAW>(sg, n, st, kernel);
+        case MD5_S16_SHIFT: return launch_coop<MD5_S16_SHIFT>(sg, n, st, kernel);
+        case MD5_S32_SHIFT: return launch_coop<MD5_S32_SHIFT>(sg, n, st, kernel);
+        case MD5_S24: return launch_coop<MD5_S24>(sg, n, st, kernel);
+        default:
+            *kernel = MD5_K_MULTI;
+            hipLaunchKernelGGL(k_md5_multi, dim3((n + 63) / 64), dim3(64), 0, st, sg);
+            return hipGetLastError();
     }
 }
 
-hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode) {
+hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hipStream_t st, int coop_mode,
+                      uint32_t* kernel) {
+    if (kernel) *kernel = 0;
     if (!n_jobs) return hipSuccess;
     if (coop_mode >= 0) {
         Md5Segs sg;
@@ -484,8 +494,9 @@ hipError_t launch_md5(const Md5Job* jobs, uint32_t n_jobs, uint32_t* digests, hi
         sg.start[0] = 0;
         sg.start[1] = n_jobs;
         sg.nseg = 1;
-        return launch_md5_multi(sg, st, coop_mode);
+        return launch_md5_multi(sg, st, coop_mode, kernel);
     }
+    if (kernel) *kernel = MD5_K_LANE;
     hipLaunchKernelGGL(k_md5, dim3((n_jobs + 63) / 64), dim3(64), 0, st, jobs, n_jobs, digests);
     return hipGetLastError();
 }

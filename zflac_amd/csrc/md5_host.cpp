@@ -85,8 +85,10 @@ static void hub_flush_runs(Md5Hub& h) {
     sg.start[sg.nseg] = n;
     for (zflac_batch* b : h.pend)  // every run gets the shared launch's time (md5_ms)
         if (b->flags & ZFLAC_FLAG_TIMING) ck(hipEventRecord(b->ev[8], hs));
-    ck(launch_md5_multi(sg, hs, coop));
+    uint32_t kernel = 0;
+    ck(launch_md5_multi(sg, hs, coop, &kernel));
     for (zflac_batch* b : h.pend) {
+        b->md5_pipe_kernel = kernel;  // every run of the flush: one launch hashes them all
         if (b->flags & ZFLAC_FLAG_TIMING) ck(hipEventRecord(b->ev[9], hs));
         ck(hipMemcpyAsync(b->pipe_pin, b->pipe_dig.p, b->pipe_who.size() * 16, hipMemcpyDeviceToHost, hs));
         ck(hipEventRecord(b->ev_md5, hs));
@@ -195,6 +197,7 @@ static bool md5_matches(const StreamState& s, const void* host_samples) {
 // more decode.
 bool md5_before_justify(zflac_batch* b, StreamState& s) {
     if (!justify_of(s.si.bps) || s.cls < 0 || (b->flags & FLAG_NO_JUSTIFY)) return false;
+    b->md5_rechecks++;  // (zflac_hip_batch_md5_stats: from here on the stream is decoded again)
     const Class& C = *b->classes[s.cls];
     const StreamDesc& D = C.desc[s.slot];
     std::vector<uint8_t> bytes(s.len);
@@ -312,7 +315,8 @@ static std::vector<uint32_t> longest_first(const std::vector<Md5Job>& jobs) {
 
 // Digest words (k_md5 layout) -> the stream's verdict; a mismatch becomes its error, as
 // decode() returns InvalidChecksum (src/zflac.zig:279-280).
-static void take_digest(StreamState& s, const uint32_t* d) {
+static void take_digest(StreamState& s, const uint32_t* d, int src) {
+    s.md5_src = src;
     for (int w = 0; w < 4; w++)
         for (int q = 0; q < 4; q++) s.md5_dig[4 * w + q] = (uint8_t)(d[w] >> (8 * q));
     s.md5_dev = std::memcmp(s.md5_dig, s.si.md5, 16) == 0 ? 1 : 2;
@@ -369,7 +373,9 @@ static void run_md5_device(zflac_batch* b, const std::vector<uint32_t>& which, b
     ck(hipMemcpyAsync(b->md5_jobs.p, sorted.data(), sorted.size() * sizeof(Md5Job), hipMemcpyHostToDevice,
                       b->stream));
     if (timing) ck(hipEventRecord(b->ev[5], b->stream));
-    ck(launch_md5(b->md5_jobs.p, (uint32_t)sorted.size(), b->md5_dig.p, b->stream, coop_mode_of(sorted)));
+    uint32_t kernel = 0;
+    ck(launch_md5(b->md5_jobs.p, (uint32_t)sorted.size(), b->md5_dig.p, b->stream, coop_mode_of(sorted), &kernel));
+    b->md5_kernels |= kernel;
     if (timing) ck(hipEventRecord(b->ev[6], b->stream));
     std::vector<uint32_t> dig(sorted.size() * 4);
     ck(hipMemcpyAsync(dig.data(), b->md5_dig.p, dig.size() * 4, hipMemcpyDeviceToHost, b->stream));
@@ -379,14 +385,15 @@ static void run_md5_device(zflac_batch* b, const std::vector<uint32_t>& which, b
         ck(hipEventElapsedTime(&t, b->ev[5], b->ev[6]));
         b->timings.md5_ms += t;
     }
-    for (size_t k = 0; k < ord.size(); k++) take_digest(b->streams[which[ord[k]]], &dig[k * 4]);
+    for (size_t k = 0; k < ord.size(); k++) take_digest(b->streams[which[ord[k]]], &dig[k * 4], ZFLAC_MD5_SRC_SYNC);
 }
 
 // After a run: the pipelined digests of the streams the run certified, then a synchronous
 // k_md5 for every other decoded stream.
 void finish_md5(zflac_batch* b, bool timing) {
     std::vector<char> done(b->streams.size(), 0);
-    for (auto& s : b->streams) s.md5_dev = 0;
+    for (auto& s : b->streams) s.md5_dev = 0, s.md5_src = ZFLAC_MD5_SRC_NONE;
+    b->md5_kernels = 0;
     if (!b->pipe_who.empty()) {
         if (timing) {
             float t = 0;
@@ -399,7 +406,8 @@ void finish_md5(zflac_batch* b, bool timing) {
             const Class& C = *b->classes[s.cls];
             if (s.err || !s.dev_samples || C.redone || C.h_status[s.slot] != 0 || (b->flags & ZFLAC_FLAG_FORCE_SLOW))
                 continue;
-            take_digest(s, b->pipe_pin + k * 4);
+            take_digest(s, b->pipe_pin + k * 4, ZFLAC_MD5_SRC_PIPELINED);
+            b->md5_kernels |= b->md5_pipe_kernel;
             done[i] = 1;
         }
     }
@@ -411,6 +419,7 @@ void finish_md5(zflac_batch* b, bool timing) {
         if (s.md5_dev == 2 && md5_before_justify(b, s)) {
             s.err = E_OK;
             s.md5_dev = 1;
+            s.md5_src = ZFLAC_MD5_SRC_HOST_RECHECK;
             std::memcpy(s.md5_dig, s.si.md5, 16);  // the digest as zflac takes it
         }
     }

@@ -570,7 +570,7 @@ void submit_batch(zflac_batch* b) {
     if (!b->pipe_who.empty() && !b->md5_hub) {  // STREAMINFO MD5 of the streams this run certifies
         const uint32_t n = (uint32_t)b->pipe_who.size();
         if (timing) ck(hipEventRecord(b->ev[8], b->rs));
-        ck(launch_md5(b->pipe_jobs.p, n, b->pipe_dig.p, b->rs, b->pipe_coop));
+        ck(launch_md5(b->pipe_jobs.p, n, b->pipe_dig.p, b->rs, b->pipe_coop, &b->md5_pipe_kernel));
         if (timing) ck(hipEventRecord(b->ev[9], b->rs));
         ck(hipMemcpyAsync(b->pipe_pin, b->pipe_dig.p, (size_t)n * 16, hipMemcpyDeviceToHost, b->rs));
     }
@@ -729,7 +729,7 @@ void finish_batch(zflac_batch* b) {
     b->timings.md5_ms = 0;
     if (b->flags & ZFLAC_FLAG_DEVICE_MD5) finish_md5(b, timing && !b->classes.empty());
     else
-        for (auto& s : b->streams) s.md5_dev = 0;
+        for (auto& s : b->streams) s.md5_dev = 0, s.md5_src = ZFLAC_MD5_SRC_NONE;
     b->timings.frames = frames;
     b->timings.input_bytes = in_bytes;
     b->timings.output_bytes = out_bytes;
