@@ -517,6 +517,53 @@ uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, 
 /* Waits for the device, then frees the plan. NULL is ignored. */
 void zflac_hip_mel_destroy(zflac_mel *m);
 
+/* The arithmetic of a plan's first product (the DFT), chosen when the plan is made.
+ *
+ * ZFLAC_MEL_MATH_F32 is zflac_hip_mel_create's plan in every respect: the same tables, kernels,
+ * bits and errors. The f32 matrix instruction runs at 1/16 of the bf16 matrix rate on gfx950; the
+ * two split modes buy that rate back by cutting both operands into bfloat16 pieces and keeping
+ * only the products that matter (kernel k_mel_split).
+ *
+ * b(v) is v rounded to the nearest bfloat16, ties to even, as ZFLAC_EXPORT_BF16 rounds. An f32 v
+ * has the pieces v0 = b(v), v1 = b(v - v0), v2 = b(v - v0 - v1); the subtractions are exact in
+ * f32 and v0 + v1 + v2 = v exactly. c_i[n][k] and s_i[n][k] are the pieces of the f32 tables c and
+ * s of zflac_hip_mel_run's definition, built on the host; x_j are the pieces of the f32 sample (or
+ * the reflected or zero value) a frame reads, taken on the device. Then
+ *   re[k] = sum_n sum_{(i,j) in T} c_i[n][k] * x_j[t * hop - off + n]      im[k] likewise with s_i
+ *   T = { i + j <= 2 }  six terms,   ZFLAC_MEL_MATH_BF16X6
+ *   T = { i + j <= 1 }  three terms, ZFLAC_MEL_MATH_BF16X3
+ * Every product is exact in f32 (8 x 8 significant bits); the sums are f32 accumulations inside
+ * the matrix cores, in the kernel's order, which is the same for every frame. Everything behind
+ * re and im is the f32 plan's: P = fmaf(im, im, re * re), the filterbank as an f32 fmaf chain over
+ * the f32 filter table, the floor, the log and the rounding to the dtype.
+ *
+ * What the dropped products cost: a sum differs from the full product c * x by at most
+ * 3 * 2^-24 * sum_n |c| |x| (BF16X6) or 2^-14 * sum_n |c| |x| (BF16X3), which is about 130 dB and
+ * 84 dB below sum_n |c| |x| in the worst case. BF16X6 is below the rounding an f32 sum of N terms
+ * has anyway and is f32-grade. The error is relative to the whole frame, not to the bin: under
+ * BF16X3 a bin more than about 80 dB below the loudest content of its frame carries no correct
+ * digit (a log-mel front end that clamps 80 dB below the maximum loses nothing it keeps; an
+ * analysis of a quiet partial beside a loud one wants BF16X6 or F32).
+ *
+ * Domain: finite samples with |x| <= 2^64; a piece below 2^-126 may be flushed to zero. Frames
+ * over a non-finite sample are unspecified; no other frame is affected. The guarantees of the f32
+ * plan hold for a split plan against itself: a frame's bits depend on the N values under it alone
+ * (not on rows, frames, first_frame, the position in a tile or the alignment of wave_device); a
+ * frame with no non-zero value under it gives exactly log(floor), or +0 on the POWER scale; a
+ * frame inside [0, n_i) has the same bits in both pad modes; a reflect run equals a zeros run of
+ * an uncentred plan of the same math over the host-reflected row, bit for bit.
+ *
+ * zflac_hip_mel_run, zflac_hip_mel_run_ex, zflac_hip_mel_frames and zflac_hip_mel_destroy take
+ * such a plan unchanged, with every rule they state (ZFLAC_NORM_ROW_MAX runs k_mel_norm as it is).
+ * An unknown math is ZFLAC_E_INVALID_ARGUMENT, checked after everything zflac_hip_mel_create
+ * checks and before the device is touched. */
+#define ZFLAC_MEL_MATH_F32    UINT32_C(0)  /* zflac_hip_mel_create's plan: the same tables, kernels, bits */
+#define ZFLAC_MEL_MATH_BF16X6 UINT32_C(1)  /* split operands, product terms of level i + j <= 2 */
+#define ZFLAC_MEL_MATH_BF16X3 UINT32_C(2)  /* split operands, product terms of level i + j <= 1 */
+int zflac_hip_mel_create_ex(const zflac_mel_desc *d, uint32_t math, int device, zflac_mel **out);
+/* The plan's ZFLAC_MEL_MATH_*; -ZFLAC_E_INVALID_ARGUMENT for NULL. */
+int zflac_hip_mel_math(const zflac_mel *m);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -576,7 +623,8 @@ const char *zflac_hip_build_id(void);
  *    zflac_mel_desc, zflac_mel, ZFLAC_MEL_*, zflac_hip_mel_create, zflac_hip_mel_run,
  *    zflac_hip_mel_frames, zflac_hip_mel_destroy; zflac_mel_run_desc, zflac_hip_mel_run_ex,
  *    ZFLAC_PAD_*, ZFLAC_NORM_*; zflac_hip_batch_md5_source, ZFLAC_MD5_SRC_*,
- *    zflac_hip_batch_md5_stats, ZFLAC_MD5_K_*. */
+ *    zflac_hip_batch_md5_stats, ZFLAC_MD5_K_*; ZFLAC_MEL_MATH_*, zflac_hip_mel_create_ex,
+ *    zflac_hip_mel_math. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

@@ -109,6 +109,9 @@ SIGNATURES = {
     "zflac_hip_mel_run_ex": (ctypes.c_int, [_P, ctypes.POINTER(zflac_mel_run_desc), _P]),
     "zflac_hip_mel_frames": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
     "zflac_hip_mel_destroy": (None, [_P]),
+    "zflac_hip_mel_create_ex": (ctypes.c_int, [ctypes.POINTER(zflac_mel_desc), ctypes.c_uint32, ctypes.c_int,
+                                               ctypes.POINTER(_P)]),
+    "zflac_hip_mel_math": (ctypes.c_int, [_P]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -145,6 +148,10 @@ MEL_LOG10 = 1
 MEL_LN = 2
 MEL_BINS_FIRST = 0
 MEL_FRAMES_FIRST = 1
+# zflac_hip_mel_create_ex: the arithmetic of the DFT (ZFLAC_MEL_MATH_*)
+MEL_MATH_F32 = 0
+MEL_MATH_BF16X6 = 1
+MEL_MATH_BF16X3 = 2
 # zflac_mel_run_desc: padding and normalisation of a run (ZFLAC_PAD_*, ZFLAC_NORM_*)
 PAD_ZEROS = 0
 PAD_REFLECT = 1

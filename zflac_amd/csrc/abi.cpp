@@ -234,7 +234,15 @@ int zflac_hip_batch_export_resampled_mixed(zflac_batch* b, const zflac_resample_
     return export_dense(b, export_call(d), mix, dst_device, dst_bytes, valid_frames, stream);
 }
 
-int zflac_hip_mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) { return mel_create(d, device, out); }
+int zflac_hip_mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) {
+    return mel_create(d, ZFLAC_MEL_MATH_F32, device, out);
+}
+
+int zflac_hip_mel_create_ex(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out) {
+    return mel_create(d, math, device, out);
+}
+
+int zflac_hip_mel_math(const zflac_mel* m) { return mel_math(m); }
 
 int zflac_hip_mel_run(zflac_mel* m, const float* wave_device, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
                       uint64_t first_frame, uint64_t frames, void* dst_device, size_t dst_bytes, void* stream) {

@@ -259,7 +259,8 @@ int export_dense(zflac_batch* b, const ExportCall& call, const zflac_mix_desc* m
 // mel_host.cpp
 // The feature plan (zflac_mel: the device tables and the plan's own stream) and its runs; the
 // argument checks, the tables and the grid rule are mel_plan.h's.
-int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out);
+int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out);
+int mel_math(const zflac_mel* m);
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream);
 int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream);

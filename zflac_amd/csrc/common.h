@@ -415,6 +415,20 @@ struct MelExArgs {
     uint32_t pad;             // ZFLAC_PAD_ZEROS / _REFLECT
 };
 
+// k_mel_split (mel_bf16.hip): the first product on the bf16 matrix cores with both operands split
+// into bf16 pieces (ZFLAC_MEL_MATH_BF16X6 / _BF16X3). The tile is k_mel's (MEL_FRAMES frames, a
+// wave MEL_TILE of them); the samples go in blocks of MEL_BF16_K, the bin tiles in groups of
+// MEL_BF16_GROUP whose accumulators are live together. The piece table's layout is mel_plan.h's.
+constexpr uint32_t MEL_BF16_K = 16;                          // samples per v_mfma_f32_32x32x16_bf16
+constexpr uint32_t MEL_BF16_GROUP = 2;                       // bin tiles per pass over the samples
+constexpr uint32_t MEL_BF16_OPERAND = 64 * 8;                // bf16 of one A operand: 64 lanes x 8
+
+struct MelSplitArgs {
+    MelExArgs e;              // e.a.basis is unused (NULL): a split plan has no f32 basis table
+    const uint16_t* pieces;   // mel_plan.h: [group][sample block][bin tile of the group][re, im][piece][lane][8]
+    uint32_t k_blocks;        // ceil(N / MEL_BF16_K)
+};
+
 constexpr uint32_t MEL_NORM_THREADS = 256;
 constexpr uint32_t MEL_NORM_CHUNK = 4096;  // elements of one row per workgroup pass
 

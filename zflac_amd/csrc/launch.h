@@ -61,4 +61,10 @@ hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a,
 hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, const MelExArgs& e, uint64_t rows, hipStream_t st);
 hipError_t launch_mel_norm(int dtype, const MelNormArgs& a, hipStream_t st);
 
+// mel_bf16.hip: k_mel_split, the tile of k_mel_ex with the first product on split bf16 operands;
+// terms is 6 (ZFLAC_MEL_MATH_BF16X6) or 3 (_BF16X3). Serves both run calls (the plain one passes
+// no lengths, no row maximum and ZFLAC_PAD_ZEROS).
+hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t terms, const MelSplitArgs& s, uint64_t rows,
+                            hipStream_t st);
+
 }  // namespace zflac

@@ -1,5 +1,5 @@
 // mel_host.cpp -- the feature plan (zflac_mel): its tables in device memory, its own stream, and
-// the launches of k_mel, k_mel_ex and k_mel_norm. A run stages nothing: the tables never change
+// the launches of k_mel, k_mel_ex and k_mel_norm, or of k_mel_split for a split-bf16 plan. A run stages nothing: the tables never change
 // and the arguments go by value, so runs of one plan on different streams may overlap.
 #include "batch.h"
 #include "launch.h"
@@ -10,6 +10,7 @@ struct zflac_mel {
     zflac::MelPlan plan;
     hipStream_t stream = nullptr;
     zflac::DevBuf<float> basis, filters;
+    zflac::DevBuf<uint16_t> pieces;  // a split plan's basis (mel_plan.h), in place of `basis`
     ~zflac_mel() {
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -17,14 +18,16 @@ struct zflac_mel {
 
 namespace zflac {
 
-int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) {
+int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out) {
     MelPlan p;
-    const int rc = mel_plan_create(d, out, p);  // the arguments first, the device afterwards
+    const int rc = mel_plan_create_ex(d, math, out, p);  // the arguments first, the device afterwards
     if (rc) return rc;
     *out = nullptr;
     return guarded([&]() -> int {
         std::vector<float> basis, filt;
-        mel_tables(p, d->window, d->filters, basis, filt);
+        std::vector<uint16_t> pieces;
+        if (p.math == ZFLAC_MEL_MATH_F32) mel_tables(p, d->window, d->filters, basis, filt);
+        else mel_bf16_tables(p, d->window, d->filters, pieces, filt);
         int count = 0;
         if (device < 0 || hipGetDeviceCount(&count) != hipSuccess || device >= count) return E_DEVICE;
         DeviceScope scope(device);
@@ -32,9 +35,14 @@ int mel_create(const zflac_mel_desc* d, int device, zflac_mel** out) {
         m->device = device;
         m->plan = p;
         ck(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->basis.alloc(basis.size());
         m->filters.alloc(filt.size());
-        ck(hipMemcpy(m->basis.p, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (p.math == ZFLAC_MEL_MATH_F32) {
+            m->basis.alloc(basis.size());
+            ck(hipMemcpy(m->basis.p, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            m->pieces.alloc(pieces.size());
+            ck(hipMemcpy(m->pieces.p, pieces.data(), pieces.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        }
         ck(hipMemcpy(m->filters.p, filt.data(), filt.size() * sizeof(float), hipMemcpyHostToDevice));
         *out = m.release();
         return E_OK;
@@ -65,6 +73,18 @@ static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_fra
     return a;
 }
 
+int mel_math(const zflac_mel* m) { return m ? (int)m->plan.math : -E_INVALID_ARGUMENT; }
+
+// A split plan's launch: one kernel for both run calls
+static hipError_t launch_split(const zflac_mel* m, const MelExArgs& e, uint64_t rows, hipStream_t st) {
+    const MelPlan& p = m->plan;
+    MelSplitArgs s;
+    s.e = e;
+    s.pieces = m->pieces.p;
+    s.k_blocks = p.k_blocks;
+    return launch_mel_split(p.dtype, p.layout, p.m_tiles, p.math == ZFLAC_MEL_MATH_BF16X6 ? 6 : 3, s, rows, st);
+}
+
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream) {
     MelGrid g;
@@ -76,7 +96,8 @@ int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames
         const MelPlan& p = m->plan;
         const MelArgs a = mel_args(m, wave, wave_frames, row_stride, first_frame, frames, dst, g);
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
-        ck(launch_mel(p.dtype, p.layout, p.m_tiles, a, rows, st));
+        if (p.math == ZFLAC_MEL_MATH_F32) ck(launch_mel(p.dtype, p.layout, p.m_tiles, a, rows, st));
+        else ck(launch_split(m, MelExArgs{a, nullptr, nullptr, ZFLAC_PAD_ZEROS}, rows, st));
         if (!stream) ck(hipStreamSynchronize(st));
         return E_OK;
     });
@@ -97,12 +118,10 @@ int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
         e.row_max = r->row_max_device;
         e.pad = r->pad;
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
-        if (mel_run_is_plain(*r)) {
-            ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, r->rows, st));
-        } else {
-            if (e.row_max) ck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e.row_max), (int)0xFF800000u, r->rows, st));
-            ck(launch_mel_ex(p.dtype, p.layout, p.m_tiles, e, r->rows, st));
-        }
+        if (e.row_max) ck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e.row_max), (int)0xFF800000u, r->rows, st));
+        if (p.math != ZFLAC_MEL_MATH_F32) ck(launch_split(m, e, r->rows, st));
+        else if (mel_run_is_plain(*r)) ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, r->rows, st));
+        else ck(launch_mel_ex(p.dtype, p.layout, p.m_tiles, e, r->rows, st));
         if (r->norm == ZFLAC_NORM_ROW_MAX) {
             MelNormArgs n;
             n.dst = r->dst_device;

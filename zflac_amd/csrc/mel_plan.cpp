@@ -2,6 +2,7 @@
 #include "mel_plan.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace zflac {
 
@@ -40,6 +41,19 @@ int mel_plan_create(const zflac_mel_desc* d, const void* out_ptr, MelPlan& p) {
     return E_OK;
 }
 
+int mel_plan_create_ex(const zflac_mel_desc* d, uint32_t math, const void* out_ptr, MelPlan& p) {
+    const int rc = mel_plan_create(d, out_ptr, p);
+    if (rc) return rc;
+    if (math != ZFLAC_MEL_MATH_F32 && math != ZFLAC_MEL_MATH_BF16X6 && math != ZFLAC_MEL_MATH_BF16X3)
+        return E_INVALID_ARGUMENT;
+    p.math = math;
+    if (math != ZFLAC_MEL_MATH_F32) {
+        p.k_blocks = (p.n_fft + MEL_BF16_K - 1) / MEL_BF16_K;
+        p.n_pieces = math == ZFLAC_MEL_MATH_BF16X6 ? 3 : 2;
+    }
+    return E_OK;
+}
+
 size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im) {
     const size_t b = k / MEL_TILE, i = k % MEL_TILE, s = n / 2, h = n % 2;
     return (((b * (p.n_fft / 2) + s) * 2 + im) * 2 + h) * MEL_TILE + i;
@@ -73,6 +87,48 @@ void mel_tables(const MelPlan& p, const float* window, const float* filters, std
     }
     for (uint32_t m = 0; m < p.n_bins; m++)
         for (uint32_t k = 0; k < K; k++) filt[mel_filter_index(p, m, k)] = filters[(size_t)m * K + k];
+}
+
+uint16_t mel_bf16_round(float v) {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+float mel_bf16_value(uint16_t h) {
+    const uint32_t u = (uint32_t)h << 16;
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+}
+
+void mel_bf16_split(float v, uint16_t h[3]) {
+    for (int i = 0; i < 3; i++) {
+        h[i] = mel_bf16_round(v);
+        v -= mel_bf16_value(h[i]);  // exact: the rest has at most 24 - 8 (i + 1) significant bits
+    }
+}
+
+size_t mel_bf16_basis_index(const MelPlan& p, uint32_t k, uint32_t n, uint32_t im, uint32_t piece) {
+    const size_t b = k / MEL_TILE, i = k % MEL_TILE, kb = n / MEL_BF16_K, h = (n % MEL_BF16_K) / 8, j = n % 8;
+    const size_t g = b / MEL_BF16_GROUP, bi = b % MEL_BF16_GROUP;
+    const size_t rest = p.bin_tiles - g * MEL_BF16_GROUP, tg = rest < MEL_BF16_GROUP ? rest : MEL_BF16_GROUP;
+    const size_t operand = ((g * MEL_BF16_GROUP * p.k_blocks + kb * tg + bi) * 2 + im) * p.n_pieces + piece;
+    return (operand * 64 + 32 * h + i) * 8 + j;
+}
+
+void mel_bf16_tables(const MelPlan& p, const float* window, const float* filters, std::vector<uint16_t>& pieces,
+                     std::vector<float>& filt) {
+    std::vector<float> basis;
+    mel_tables(p, window, filters, basis, filt);  // c and s as the f32 plan holds them
+    pieces.assign(p.piece_elems(), 0);
+    for (uint32_t n = 0; n < p.n_fft; n++)
+        for (uint32_t k = 0; k < p.K; k++)
+            for (uint32_t im = 0; im < 2; im++) {
+                uint16_t h[3];
+                mel_bf16_split(basis[mel_basis_index(p, n, k, im)], h);
+                for (uint32_t i = 0; i < p.n_pieces; i++) pieces[mel_bf16_basis_index(p, k, n, im, i)] = h[i];
+            }
 }
 
 int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,

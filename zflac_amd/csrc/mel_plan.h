@@ -19,6 +19,19 @@
 //            of the tile in lanes 0..31 and that row + 4 in lanes 32..63: P's register r is the
 //            B operand of one MFMA as it stands, against this A operand.
 //            The filter tiles are m_tiles = 1, 2, 4 or 8 (the least that holds n_bins).
+//
+// A split plan (ZFLAC_MEL_MATH_BF16X6 / _BF16X3, k_mel_split) has no f32 basis table. Its first
+// product runs on v_mfma_f32_32x32x16_bf16 (16 terms of the sum per instruction: lane l holds
+// A[row l & 31][k = 8 (l >> 5) + j], j = 0..7, eight bf16 = 16 bytes), over the bf16 pieces
+// v0 = b(v), v1 = b(v - v0), v2 = b(v - v0 - v1) of the f32 entries of c and s:
+//
+//   pieces   [group g][sample block kb][bin tile bi of the group][re, im][piece][lane l][j]
+//            = piece of c or s [16 kb + 8 (l >> 5) + j][32 (G g + bi) + (l & 31)], G = MEL_BF16_GROUP,
+//            zero for samples >= N (N is padded to a multiple of 16) and bins >= K. A group holds
+//            G bin tiles, the last the rest, and nothing is stored for the tiles it lacks: the
+//            512 bf16 of one (bin tile, re/im, piece) are the A operand of one MFMA, one 16-byte
+//            read per lane, and everything one sample block of a group needs is contiguous, so
+//            it goes to LDS as a plain copy. BF16X6 stores three pieces, BF16X3 the two it uses.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -40,7 +53,11 @@ struct MelPlan {
     uint32_t K = 0;          // N / 2 + 1
     uint32_t bin_tiles = 0;  // ceil(K / MEL_TILE)
     uint32_t m_tiles = 0;    // filter tiles: 1, 2, 4 or 8
+    uint32_t math = ZFLAC_MEL_MATH_F32;
+    uint32_t k_blocks = 0;   // ceil(N / MEL_BF16_K): sample blocks of a split plan
+    uint32_t n_pieces = 0;   // bf16 pieces of a basis entry in the table: 3 (BF16X6), 2 (BF16X3), 0 (F32)
     size_t basis_floats() const { return (size_t)bin_tiles * n_fft * 2 * MEL_TILE; }
+    size_t piece_elems() const { return (size_t)bin_tiles * k_blocks * 2 * n_pieces * MEL_BF16_OPERAND; }
     size_t filter_floats() const { return (size_t)bin_tiles * 16 * m_tiles * 64; }
     size_t elem_size() const { return dtype == ZFLAC_EXPORT_F32 ? 4 : 2; }
 };
@@ -52,6 +69,8 @@ constexpr uint32_t mel_acc_row(uint32_t r) { return (r & 3) + 8 * (r >> 2); }
 // compared with NULL); size; dtype, layout, scale, center; n_fft; hop; n_bins; reserved; floor;
 // window and filters (NULL, then every value finite). E_OK fills p; nothing else is touched.
 int mel_plan_create(const zflac_mel_desc* d, const void* out_ptr, MelPlan& p);
+// zflac_hip_mel_create_ex's: everything above, in that order, then math (a known ZFLAC_MEL_MATH_*)
+int mel_plan_create_ex(const zflac_mel_desc* d, uint32_t math, const void* out_ptr, MelPlan& p);
 
 // Where the kernel's tables hold c[n][k] (im = 0) or s[n][k] (im = 1), and filters[m][k]
 size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im);
@@ -59,6 +78,19 @@ size_t mel_filter_index(const MelPlan& p, uint32_t m, uint32_t k);
 // Both tables, p.basis_floats() and p.filter_floats() long, zero wherever no (n, k) or (m, k) lands
 void mel_tables(const MelPlan& p, const float* window, const float* filters, std::vector<float>& basis,
                 std::vector<float>& filt);
+
+// bf16 rounded to nearest-even from an f32 (ties to the even bf16; no NaNs here), and its f32 value
+uint16_t mel_bf16_round(float v);
+float mel_bf16_value(uint16_t h);
+// The pieces of an f32: h[i] = b(v - h[0] - .. - h[i - 1]); the three sum to v exactly
+void mel_bf16_split(float v, uint16_t h[3]);
+// Where a split plan's table holds piece `piece` (< p.n_pieces) of c[n][k] (im = 0) or s[n][k]
+// (im = 1), n < 16 p.k_blocks, k < 32 p.bin_tiles: the layout's single definition
+size_t mel_bf16_basis_index(const MelPlan& p, uint32_t k, uint32_t n, uint32_t im, uint32_t piece);
+// A split plan's tables: p.piece_elems() bf16 pieces of the entries mel_tables gives the f32 plan
+// of the same descriptor, and its filter table unchanged
+void mel_bf16_tables(const MelPlan& p, const float* window, const float* filters, std::vector<uint16_t>& pieces,
+                     std::vector<float>& filt);
 
 struct MelGrid {
     uint32_t tiles = 0;   // workgroups per row: ceil(frames / MEL_FRAMES)

@@ -315,6 +315,7 @@ def mel_filters(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="sl
 _MEL_SCALES = {"power": _lib.MEL_POWER, "log10": _lib.MEL_LOG10, "ln": _lib.MEL_LN}
 _MEL_LAYOUTS = {"bins_first": _lib.MEL_BINS_FIRST, "frames_first": _lib.MEL_FRAMES_FIRST}
 _MEL_PADS = {"zeros": _lib.PAD_ZEROS, "reflect": _lib.PAD_REFLECT}
+_MEL_MATHS = {"f32": _lib.MEL_MATH_F32, "bf16x6": _lib.MEL_MATH_BF16X6, "bf16x3": _lib.MEL_MATH_BF16X3}
 
 
 class MelSpectrogram:
@@ -342,25 +343,33 @@ class MelSpectrogram:
     computes them) before rounding to dtype; a log scale only. The maxima of the last call are
     mel.last_row_max ([B] or [B, C] float32), or the third result with return_row_max=True.
     With the defaults a call is one zflac_hip_mel_run, as before.
+    math: the arithmetic of the DFT (zflac_hip_mel_create_ex). "f32" (the default): f32 on the
+    matrix cores, as ever. "bf16x6" / "bf16x3": both operands split into bfloat16 pieces, six or
+    three piece products kept, on the 16 times faster bf16 matrix cores (k_mel_split): a sum is
+    within 3 * 2^-24 (f32-grade) or 2^-14 (about 84 dB) of sum |c| |x| of the full product; a bin
+    further than that below its frame's loudest content is noise under "bf16x3". mel.math reads
+    the plan's mode back from the library.
     The object owns a plan of the library: close() it, or use it in `with`."""
 
     @classmethod
-    def whisper(cls, n_mels=80, device=0, dtype=torch.float32):
+    def whisper(cls, n_mels=80, device=0, dtype=torch.float32, math="f32"):
         """Whisper's front end: 16 kHz, n_fft 400, hop 160, the periodic Hann window, the Slaney
         filterbank, log10 with floor 1e-10, reflect padding at the end of the row, and
         (max(x, M - 8) + 4) / 4. Whisper's rows are 30 s (480,000 samples, zero-filled behind the
         audio) and it drops the STFT's last frame: call the plan with frames=3000, which also
         keeps that frame out of M. The result is the encoder's input [B, n_mels, 3000]."""
         return cls(16000, 400, 160, n_mels, scale="log10", floor=1e-10, center=True, dtype=dtype, device=device,
-                   pad="reflect", normalize=(8.0, 4.0, 0.25), reflect_at="end")
+                   pad="reflect", normalize=(8.0, 4.0, 0.25), reflect_at="end", math=math)
 
     def __init__(self, sample_rate, n_fft=400, hop=160, n_mels=80, window="hann", filters=None, scale="log10",
                  floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, pad="zeros",
-                 normalize=None, reflect_at="length", **filter_kw):
-        import math
+                 normalize=None, reflect_at="length", math="f32", **filter_kw):
+        import math as _math
 
         import numpy as np
 
+        if math not in _MEL_MATHS:
+            raise ValueError("math is 'f32', 'bf16x6' or 'bf16x3'")
         check_single_runtime()
         if pad not in _MEL_PADS:
             raise ValueError("pad is 'zeros' or 'reflect'")
@@ -370,7 +379,7 @@ class MelSpectrogram:
             raise ValueError("reflect_at is 'length' or 'end'")
         if normalize is not None:
             normalize = tuple(float(v) for v in normalize)
-            if len(normalize) != 3 or not all(math.isfinite(v) for v in normalize) or normalize[0] < 0 or normalize[2] == 0:
+            if len(normalize) != 3 or not all(_math.isfinite(v) for v in normalize) or normalize[0] < 0 or normalize[2] == 0:
                 raise ValueError("normalize is (range >= 0, add, mul != 0), all finite")
             if scale == "power":
                 raise ValueError("normalize needs a log scale")
@@ -414,7 +423,14 @@ class MelSpectrogram:
                                    w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                    fb.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         self._h = ctypes.c_void_p()
-        errors.check(self._L.zflac_hip_mel_create(ctypes.byref(desc), self.device, ctypes.byref(self._h)), "mel_create")
+        errors.check(self._L.zflac_hip_mel_create_ex(ctypes.byref(desc), _MEL_MATHS[math], self.device,
+                                                     ctypes.byref(self._h)), "mel_create_ex")
+
+    @property
+    def math(self):
+        """The plan's arithmetic as the library reports it (zflac_hip_mel_math): "f32", "bf16x6" or "bf16x3"."""
+        code = self._L.zflac_hip_mel_math(self._h)
+        return next(k for k, v in _MEL_MATHS.items() if v == code)
 
     def mel_frames(self, n_samples):
         """Frames of a row of n_samples (zflac_hip_mel_frames): an int, or a tensor for a tensor."""
