@@ -564,6 +564,110 @@ int zflac_hip_mel_create_ex(const zflac_mel_desc *d, uint32_t math, int device, 
 /* The plan's ZFLAC_MEL_MATH_*; -ZFLAC_E_INVALID_ARGUMENT for NULL. */
 int zflac_hip_mel_math(const zflac_mel *m);
 
+/* Framed plans: a frame shorter than the DFT, Kaldi's framings, and the per-frame operations of
+ * a Kaldi filterbank front end folded into the tables. N = d->n_fft is the DFT size, K = N / 2 + 1,
+ * Nw = f->win_length the frame length, and d->window holds Nw floats.
+ *
+ * Frame start. Frame t reads x_i[s0(t) + n], n < Nw:
+ *   ZFLAC_FRAMING_STFT          s0(t) = t hop - (center ? N / 2 : 0) + (N - Nw) / 2: torch.stft with
+ *                               the window centred in the DFT; frames: zflac_hip_mel_frames's.
+ *   ZFLAC_FRAMING_SNIP          s0(t) = t hop; frames: n >= Nw ? (n - Nw) / hop + 1 : 0 (Kaldi,
+ *                               snip_edges = true). center must be 0.
+ *   ZFLAC_FRAMING_KALDI_CENTER  s0(t) = t hop + hop / 2 - Nw / 2 (integer divisions); frames:
+ *                               (n + hop / 2) / hop (Kaldi, snip_edges = false). center must be 0.
+ * hop <= Nw for every framed plan. s0(0) may be positive (_STFT, center = 0, Nw < N).
+ *
+ * Frame operator, in Kaldi's order, on f[n] = g x_i[s0 + n] (g = sample_scale):
+ *   1. remove_dc:    f[n] -= mean(f)
+ *   2. preemphasis:  y[0] = (1 - a) f[0],  y[n] = f[n] - a f[n - 1]
+ *   3. window:       z[n] = window[n] y[n]
+ *   4. z zero-extended to N, its DFT, the power P[k] = |Z[k]|^2, then as zflac_hip_mel_run.
+ * z = A x is linear in the frame, so the library folds A into the tables and the kernels run the
+ * sums of zflac_hip_mel_run unchanged over Nw terms:
+ *   re[k] = sum_{n < Nw} c'[n][k] x_i[s0 + n]
+ *   c'[n][k] = (float)( sum_m window[m] cos(2 pi ((m k) mod N) / N) A[m][n] ),  s' with -sin,
+ * built in double and rounded once (the sine entries of k = 0 and k = N / 2 are exactly 0 before
+ * the folding, as ever). The window sits at n = 0..Nw-1 of the DFT, not centred in it: the power
+ * spectrum does not see that shift, so a framed plan agrees with the plan of the same window
+ * zero-padded to N within the error bound of the sums, not bit for bit.
+ * The table is padded with zero rows to an even Nw (F32) or a multiple of 16 (split plans); a
+ * padded position may read a real sample against a zero coefficient, which adds nothing for a
+ * finite sample (non-finite samples: the split plans' "unspecified" clause holds for both).
+ *
+ * A framed plan with Nw = N, ZFLAC_FRAMING_STFT, remove_dc = 0, preemphasis = 0 and
+ * sample_scale = 1 is zflac_hip_mel_create_ex's plan: the same tables byte for byte, the same
+ * kernels, the same bits. zflac_hip_mel_run, _run_ex, _math and _destroy take a framed plan.
+ * ZFLAC_PAD_REFLECT needs ZFLAC_FRAMING_STFT with center = 1 and pads by N / 2, half the DFT
+ * size, as torch.stft does. ZFLAC_PAD_MIRROR (zflac_mel_run_desc.pad; ZFLAC_FRAMING_KALDI_CENTER
+ * only) reads xm_i[s] in place of x_i[s]:
+ *   xm_i[s] = x_i[rho(s)] if 0 <= rho(s) < n_i, else 0
+ *   rho(s) = -1 - s for s < 0,  2 n_i - 1 - s for s >= n_i,  s otherwise
+ * (the edge sample is repeated). One mirror, a total function: Kaldi's ExtractWindow wherever one
+ * reflection suffices, zeros where Kaldi would reflect again. ZFLAC_PAD_ZEROS works with every
+ * framing. A frame inside [0, n_i) has the same bits in every pad mode.
+ *
+ * Checked, in this order, before the device is touched (ZFLAC_E_INVALID_ARGUMENT): everything
+ * zflac_hip_mel_create checks up to and including floor, then f (NULL), f->size, win_length
+ * (1..n_fft), framing, remove_dc (0 or 1), preemphasis (finite, 0 <= a <= 1), sample_scale
+ * (finite, 2^-64 <= |g| <= 2^64), reserved; window and filters (NULL, then every value finite,
+ * window read as Nw floats); framing against center; hop <= Nw; math.
+ *
+ * Not provided: dither (0 only), use_energy / raw_energy, VTLN warping, and pre-emphasis over the
+ * whole waveform (NeMo's); the pre-emphasis here is Kaldi's, per frame. */
+#define ZFLAC_FRAMING_STFT         0
+#define ZFLAC_FRAMING_SNIP         1
+#define ZFLAC_FRAMING_KALDI_CENTER 2
+#define ZFLAC_PAD_MIRROR 2
+typedef struct zflac_mel_frame_desc {
+    uint32_t size;          /* sizeof(zflac_mel_frame_desc): 20 */
+    uint16_t win_length;    /* Nw: 1..n_fft; desc->window then has Nw floats */
+    uint8_t  framing;       /* ZFLAC_FRAMING_* */
+    uint8_t  remove_dc;     /* 0 or 1 */
+    float    preemphasis;   /* a: finite, 0 <= a <= 1 */
+    float    sample_scale;  /* g: finite, 2^-64 <= |g| <= 2^64 (1 = none, 32768 = Kaldi's 16-bit scale) */
+    uint32_t reserved;      /* must be 0 */
+} zflac_mel_frame_desc;
+int zflac_hip_mel_create_framed(const zflac_mel_desc *d, const zflac_mel_frame_desc *f,
+                                uint32_t math, int device, zflac_mel **out);
+/* Frames of a row of n_samples under the plan's framing (the table above). 0 for NULL. Host
+ * arithmetic. */
+uint64_t zflac_hip_mel_plan_frames(const zflac_mel *m, uint64_t n_samples);
+
+/* Mean / variance normalisation of each (row, bin) over the row's valid frames, in place, behind
+ * zflac_hip_mel_run / _run_ex (utterance CMVN; kernel k_mel_cmvn). feat_device is rows x n_bins x
+ * frames elements of the plan's dtype in the plan's layout. F_i = min(valid_device[i], frames), or
+ * frames for every row when valid_device is NULL. With l[j] the stored element of (row i, bin b)
+ * at frame j widened to f32:
+ *   mu = sum_{j < F_i} l[j] / F_i
+ *   var = sum_{j < F_i} (l[j] - mu)^2 / max(F_i - ddof, 0),  sigma = sqrt(var), 0 when the divisor is 0
+ * Both sums are f64, in an order that is a function of F_i alone (and of the plan): no floating
+ * atomics, so a run repeats bit for bit and a row's bits do not depend on the row count or on the
+ * row's position. mu32 = (float)mu; r = (float)(1 / (sigma + eps)), 0 when sigma + eps = 0, and 1
+ * for ZFLAC_CMVN_MEAN. Stored at j < F_i: conv((l[j] - mu32) * r), two f32 roundings, nothing
+ * fused; at j >= F_i: conv(pad_value). mean_device / std_device (rows x n_bins f32, optional)
+ * receive mu32 and (float)sigma (std: 0 for ZFLAC_CMVN_MEAN); both are 0 where F_i = 0. The
+ * statistics depend on the frame window the caller hands over, as the row maximum does.
+ * Stream semantics are zflac_hip_mel_run_ex's; nothing is staged from the host. rows == 0:
+ * ZFLAC_OK, nothing done.
+ * ZFLAC_E_INVALID_ARGUMENT (nothing enqueued), in this order: NULL m or c; size; mode; ddof > 1;
+ * reserved; NULL feat_device; frames == 0; rows * n_bins * frames * element size not fitting 63
+ * bits; valid_device not 8-byte, mean_device or std_device not 4-byte aligned; eps not finite or
+ * negative; pad_value not finite. */
+#define ZFLAC_CMVN_MEAN 0
+#define ZFLAC_CMVN_MEAN_VAR 1
+typedef struct zflac_mel_cmvn_desc {
+    uint32_t size;                  /* sizeof(zflac_mel_cmvn_desc): 64 on LP64 */
+    uint8_t mode, ddof;             /* ZFLAC_CMVN_*; 0 or 1 */
+    uint16_t reserved;              /* must be 0 */
+    void *feat_device;              /* rows x n_bins x frames of the plan's dtype and layout, in place */
+    uint64_t rows, frames;
+    const uint64_t *valid_device;   /* per row, valid frames; or NULL: frames */
+    float *mean_device, *std_device;/* optional outputs, rows x n_bins f32; may be NULL */
+    float eps;                      /* finite, >= 0 */
+    float pad_value;                /* finite; stored in frames >= F_i */
+} zflac_mel_cmvn_desc;
+int zflac_hip_mel_cmvn(zflac_mel *m, const zflac_mel_cmvn_desc *c, void *stream);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -624,7 +728,9 @@ const char *zflac_hip_build_id(void);
  *    zflac_hip_mel_frames, zflac_hip_mel_destroy; zflac_mel_run_desc, zflac_hip_mel_run_ex,
  *    ZFLAC_PAD_*, ZFLAC_NORM_*; zflac_hip_batch_md5_source, ZFLAC_MD5_SRC_*,
  *    zflac_hip_batch_md5_stats, ZFLAC_MD5_K_*; ZFLAC_MEL_MATH_*, zflac_hip_mel_create_ex,
- *    zflac_hip_mel_math. */
+ *    zflac_hip_mel_math; zflac_mel_frame_desc, ZFLAC_FRAMING_*, ZFLAC_PAD_MIRROR,
+ *    zflac_hip_mel_create_framed, zflac_hip_mel_plan_frames; zflac_mel_cmvn_desc, ZFLAC_CMVN_*,
+ *    zflac_hip_mel_cmvn. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

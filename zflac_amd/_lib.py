@@ -67,6 +67,19 @@ class zflac_mel_run_desc(ctypes.Structure):
                 ("add", ctypes.c_float), ("mul", ctypes.c_float), ("reserved2", ctypes.c_uint32)]
 
 
+class zflac_mel_frame_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("win_length", ctypes.c_uint16), ("framing", ctypes.c_uint8),
+                ("remove_dc", ctypes.c_uint8), ("preemphasis", ctypes.c_float), ("sample_scale", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
+class zflac_mel_cmvn_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("mode", ctypes.c_uint8), ("ddof", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16), ("feat_device", ctypes.c_void_p), ("rows", ctypes.c_uint64),
+                ("frames", ctypes.c_uint64), ("valid_device", ctypes.c_void_p), ("mean_device", ctypes.c_void_p),
+                ("std_device", ctypes.c_void_p), ("eps", ctypes.c_float), ("pad_value", ctypes.c_float)]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -112,6 +125,10 @@ SIGNATURES = {
     "zflac_hip_mel_create_ex": (ctypes.c_int, [ctypes.POINTER(zflac_mel_desc), ctypes.c_uint32, ctypes.c_int,
                                                ctypes.POINTER(_P)]),
     "zflac_hip_mel_math": (ctypes.c_int, [_P]),
+    "zflac_hip_mel_create_framed": (ctypes.c_int, [ctypes.POINTER(zflac_mel_desc), ctypes.POINTER(zflac_mel_frame_desc),
+                                                   ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(_P)]),
+    "zflac_hip_mel_plan_frames": (ctypes.c_uint64, [_P, ctypes.c_uint64]),
+    "zflac_hip_mel_cmvn": (ctypes.c_int, [_P, ctypes.POINTER(zflac_mel_cmvn_desc), _P]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -155,6 +172,14 @@ MEL_MATH_BF16X3 = 2
 # zflac_mel_run_desc: padding and normalisation of a run (ZFLAC_PAD_*, ZFLAC_NORM_*)
 PAD_ZEROS = 0
 PAD_REFLECT = 1
+PAD_MIRROR = 2  # a ZFLAC_FRAMING_KALDI_CENTER plan only
+# zflac_mel_frame_desc: where a frame starts and how frames are counted (ZFLAC_FRAMING_*)
+FRAMING_STFT = 0
+FRAMING_SNIP = 1
+FRAMING_KALDI_CENTER = 2
+# zflac_mel_cmvn_desc (ZFLAC_CMVN_*)
+CMVN_MEAN = 0
+CMVN_MEAN_VAR = 1
 NORM_NONE = 0
 NORM_ROW_MAX = 1
 # zflac_hip_batch_decode_buckets: one bit per k_decode history bucket (ZFLAC_BUCKET_*)

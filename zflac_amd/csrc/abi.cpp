@@ -244,6 +244,15 @@ int zflac_hip_mel_create_ex(const zflac_mel_desc* d, uint32_t math, int device, 
 
 int zflac_hip_mel_math(const zflac_mel* m) { return mel_math(m); }
 
+int zflac_hip_mel_create_framed(const zflac_mel_desc* d, const zflac_mel_frame_desc* f, uint32_t math, int device,
+                                zflac_mel** out) {
+    return mel_create_framed(d, f, math, device, out);
+}
+
+uint64_t zflac_hip_mel_plan_frames(const zflac_mel* m, uint64_t n_samples) { return mel_plan_frames_of(m, n_samples); }
+
+int zflac_hip_mel_cmvn(zflac_mel* m, const zflac_mel_cmvn_desc* c, void* stream) { return mel_cmvn(m, c, stream); }
+
 int zflac_hip_mel_run(zflac_mel* m, const float* wave_device, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
                       uint64_t first_frame, uint64_t frames, void* dst_device, size_t dst_bytes, void* stream) {
     return mel_run(m, wave_device, rows, wave_frames, row_stride, first_frame, frames, dst_device, dst_bytes, stream);

@@ -260,6 +260,10 @@ int export_dense(zflac_batch* b, const ExportCall& call, const zflac_mix_desc* m
 // The feature plan (zflac_mel: the device tables and the plan's own stream) and its runs; the
 // argument checks, the tables and the grid rule are mel_plan.h's.
 int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out);
+// f != NULL: zflac_hip_mel_create_framed
+int mel_create_framed(const zflac_mel_desc* d, const zflac_mel_frame_desc* f, uint32_t math, int device, zflac_mel** out);
+uint64_t mel_plan_frames_of(const zflac_mel* m, uint64_t n_samples);
+int mel_cmvn(zflac_mel* m, const zflac_mel_cmvn_desc* c, void* stream);
 int mel_math(const zflac_mel* m);
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream);

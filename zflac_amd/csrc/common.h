@@ -400,9 +400,10 @@ struct MelArgs {
     uint64_t first_frame;  // feature frame of destination frame 0
     uint64_t frames;       // destination frames per row
     uint32_t tiles;        // workgroups per row: ceil(frames / MEL_FRAMES); grid = rows * tiles
-    uint32_t n_fft, hop, off;  // N, hop, center ? N / 2 : 0
+    uint32_t n_fft, hop;   // the frame span the sums run over (N; a framed plan: Nw, padded as its table), hop
+    int32_t off;           // frame t starts at sample t * hop - off (center ? N / 2 : 0; a framed plan: mel_plan.h)
     uint32_t n_bins;       // rows of the filterbank
-    uint32_t bin_tiles;    // ceil((N / 2 + 1) / MEL_TILE)
+    uint32_t bin_tiles;    // ceil((N / 2 + 1) / MEL_TILE), N the DFT size
     uint32_t scale;        // ZFLAC_MEL_POWER / _LOG10 / _LN
     float floor;
 };
@@ -412,7 +413,8 @@ struct MelExArgs {
     MelArgs a;
     const uint64_t* lengths;  // per row, clamped to a.wave_frames; NULL = a.wave_frames
     float* row_max;           // per row, -inf before the launch; NULL = not wanted
-    uint32_t pad;             // ZFLAC_PAD_ZEROS / _REFLECT
+    uint32_t pad;             // ZFLAC_PAD_ZEROS / _REFLECT / _MIRROR
+    uint32_t pad_half;        // _REFLECT: the padded signal is [-pad_half, n_i + pad_half): half the DFT size
 };
 
 // k_mel_split (mel_bf16.hip): the first product on the bf16 matrix cores with both operands split
@@ -439,6 +441,23 @@ struct MelNormArgs {
     uint64_t chunks;       // per row: ceil(row_elems / MEL_NORM_CHUNK)
     uint64_t total;        // rows * chunks
     float range, add, mul;
+};
+
+// k_mel_cmvn (mel_cmvn.hip): per (row, bin) mean / variance normalisation over the valid frames,
+// in place. Bins-first: a workgroup pass takes one (row, bin), frames contiguous elements.
+// Frames-first: a pass takes one row, the bins on the lanes.
+constexpr uint32_t MEL_CMVN_THREADS = 256;
+
+struct MelCmvnArgs {
+    void* feat;             // rows x n_bins x frames (or rows x frames x n_bins) elements of the dtype
+    const uint64_t* valid;  // per row, clamped to frames; NULL = frames
+    float* mean;            // rows x n_bins, or NULL
+    float* std;             // rows x n_bins, or NULL
+    uint64_t rows, frames;
+    uint64_t total;         // passes: rows * n_bins (bins first) or rows (frames first)
+    uint32_t n_bins;
+    uint32_t mode, ddof;    // ZFLAC_CMVN_*; 0 or 1
+    float eps, pad_value;
 };
 
 }  // namespace zflac

@@ -57,14 +57,21 @@ hipError_t launch_resample_mixed(int dtype, int layout, const ResampleArgs& a, c
 
 // mel.hip: k_mel over rows * a.tiles workgroups; m_tiles is the plan's filter tile count (1, 2, 4 or 8)
 hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st);
-// k_mel_ex (lengths, reflect padding, the row maximum) over the same grid; k_mel_norm over a.total passes
-hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, const MelExArgs& e, uint64_t rows, hipStream_t st);
+// k_mel_ex (lengths, reflect padding, the row maximum) over the same grid (framed: as for
+// launch_mel_split below); k_mel_norm over a.total passes
+hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, bool framed, const MelExArgs& e, uint64_t rows,
+                         hipStream_t st);
 hipError_t launch_mel_norm(int dtype, const MelNormArgs& a, hipStream_t st);
 
 // mel_bf16.hip: k_mel_split, the tile of k_mel_ex with the first product on split bf16 operands;
 // terms is 6 (ZFLAC_MEL_MATH_BF16X6) or 3 (_BF16X3). Serves both run calls (the plain one passes
-// no lengths, no row maximum and ZFLAC_PAD_ZEROS).
-hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t terms, const MelSplitArgs& s, uint64_t rows,
-                            hipStream_t st);
+// no lengths, no row maximum and ZFLAC_PAD_ZEROS). framed: the plan's frame is not the whole
+// DFT in STFT framing (MelPlan::framed): the instantiations with a signed start offset, the DFT
+// size's reflect bound and ZFLAC_PAD_MIRROR; the others are the kernel as it was.
+hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t terms, bool framed, const MelSplitArgs& s,
+                            uint64_t rows, hipStream_t st);
+
+// mel_cmvn.hip: k_mel_cmvn over a.total passes, at most 2^31 - 1 workgroups
+hipError_t launch_mel_cmvn(int dtype, int layout, const MelCmvnArgs& a, hipStream_t st);
 
 }  // namespace zflac

@@ -54,9 +54,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One workgroup's tile. EX = false is zflac_hip_mel_run's kernel as it always was; EX = true
-// (zflac_hip_mel_run_ex) adds the row's own length, reflect padding and the row maximum.
-template <int DT, int LAYOUT, int MT, bool EX>
-__device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengths, float* row_max, uint32_t pad) {
+// (zflac_hip_mel_run_ex) adds the row's own length, reflect padding and the row maximum. FR (with
+// EX): a framed plan, whose reflect bound is half the DFT size rather than half the span and which
+// may ask for ZFLAC_PAD_MIRROR; FR = false is k_mel_ex as it was before framed plans, statement for
+// statement, so the plans that existed run the code they had.
+template <int DT, int LAYOUT, int MT, bool EX, bool FR>
+__device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengths, float* row_max, uint32_t pad,
+                                         uint32_t pad_half) {
     using OT = typename Out<DT>::T;
     __shared__ __attribute__((aligned(16))) float lds[MEL_LDS_FLOATS];
     float* const lb = lds;                               // basis slab
@@ -65,18 +69,19 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
     const uint64_t row = blockIdx.x / a.tiles;
     const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
     const float* const x = a.wave + row * a.row_stride;
-    const uint32_t N = a.n_fft;
+    const uint32_t N = a.n_fft;  // the frame span: the DFT size, or a framed plan's (padded) frame length
     // the row's length, and whether this tile needs the reflection: both uniform, decided once.
     // An interior tile (every sample index of its 128 frames inside [0, n_row)) stages as ever.
     uint64_t n_row = a.wave_frames;
     bool edge = false;
+    const int64_t off = EX && !FR ? (int64_t)(uint32_t)a.off : (int64_t)a.off;  // (negative for some framed plans)
     if constexpr (EX) {
         if (lengths) {
             const uint64_t n = lengths[row];
             n_row = n < a.wave_frames ? n : a.wave_frames;
         }
-        if (pad == ZFLAC_PAD_REFLECT) {
-            const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - (int64_t)a.off;
+        if (FR ? pad != ZFLAC_PAD_ZEROS : pad == ZFLAC_PAD_REFLECT) {
+            const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - off;
             edge = lo < 0 || (uint64_t)lo + (uint64_t)(MEL_FRAMES - 1) * a.hop + N > n_row;
         }
     }
@@ -89,7 +94,7 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
     for (uint32_t g = 0; g < MEL_WAVES; g++) {
         const uint64_t j = j0 + st_j + MEL_TILE * g;
         st_ok[g] = j < a.frames;
-        st_base[g] = st_ok[g] ? (int64_t)((a.first_frame + j) * a.hop) - (int64_t)a.off : 0;
+        st_base[g] = st_ok[g] ? (int64_t)((a.first_frame + j) * a.hop) - off : 0;
     }
 
     f32x16 V[MT];
@@ -110,13 +115,16 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
             for (uint32_t i = tid * 4; i < ns * (2 * MEL_TILE); i += MEL_THREADS * 4)
                 *reinterpret_cast<f32x4*>(lb + i) = *reinterpret_cast<const f32x4*>(bs + i);
             if (EX && edge) {  // x~[s] = x[rho(s)]: one reflection about 0 or n_row - 1, zero beyond it
-                const int64_t nr = (int64_t)n_row, half = (int64_t)(N / 2);
+                // _REFLECT: rho(s) = -s, 2 (n_row - 1) - s, inside the signal padded by half the DFT size;
+                // _MIRROR repeats the edge sample (m = 1): rho(s) = -1 - s, 2 n_row - 1 - s, no other bound
+                const int64_t nr = (int64_t)n_row, m = FR && pad == ZFLAC_PAD_MIRROR;
+                const int64_t half = !FR ? (int64_t)(N / 2) : m ? (int64_t)1 << 62 : (int64_t)pad_half;
                 for (uint32_t n = st_n; n < ns; n += 8) {
                     float v[MEL_WAVES];
 #pragma unroll
                     for (uint32_t g = 0; g < MEL_WAVES; g++) {
                         const int64_t s = st_base[g] + (int64_t)(n0 + n);
-                        const int64_t r = s < 0 ? -s : (s >= nr ? 2 * (nr - 1) - s : s);
+                        const int64_t r = s < 0 ? -s - m : (s >= nr ? 2 * (nr - 1) + m - s : s);
                         v[g] = st_ok[g] && s >= -half && s < nr + half && r >= 0 && r < nr ? x[r] : 0.0f;
                     }
 #pragma unroll
@@ -199,12 +207,12 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
 
 template <int DT, int LAYOUT, int MT>
 __global__ __launch_bounds__(MEL_THREADS) void k_mel(MelArgs a) {
-    mel_tile<DT, LAYOUT, MT, false>(a, nullptr, nullptr, 0);
+    mel_tile<DT, LAYOUT, MT, false, false>(a, nullptr, nullptr, 0, 0);
 }
 
-template <int DT, int LAYOUT, int MT>
+template <int DT, int LAYOUT, int MT, bool FR>
 __global__ __launch_bounds__(MEL_THREADS) void k_mel_ex(MelExArgs e) {
-    mel_tile<DT, LAYOUT, MT, true>(e.a, e.lengths, e.row_max, e.pad);
+    mel_tile<DT, LAYOUT, MT, true, FR>(e.a, e.lengths, e.row_max, e.pad, e.pad_half);
 }
 
 // k_mel_norm: (max(l, M_row - range) + add) * mul over the destination in place, every operation
@@ -260,11 +268,12 @@ __global__ __launch_bounds__(MEL_NORM_THREADS) void k_mel_norm(MelNormArgs a) {
     }
 }
 
-template <int DT, int LAYOUT, bool EX, typename A>
+// EX: 0 k_mel, 1 k_mel_ex as it was, 2 k_mel_ex of a framed plan
+template <int DT, int LAYOUT, int EX, typename A>
 hipError_t launch_mt(uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
-#define ZFLAC_MEL_LAUNCH(MT)                                                                              \
-    if constexpr (EX) hipLaunchKernelGGL((k_mel_ex<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); \
-    else hipLaunchKernelGGL((k_mel<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a);             \
+#define ZFLAC_MEL_LAUNCH(MT)                                                                                          \
+    if constexpr (EX) hipLaunchKernelGGL((k_mel_ex<DT, LAYOUT, MT, EX == 2>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); \
+    else hipLaunchKernelGGL((k_mel<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a);                         \
     break
     switch (m_tiles) {
         case 1: ZFLAC_MEL_LAUNCH(1);
@@ -277,13 +286,13 @@ hipError_t launch_mt(uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t 
     return hipGetLastError();
 }
 
-template <int DT, bool EX, typename A>
+template <int DT, int EX, typename A>
 hipError_t launch_dt(int layout, uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
     return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, EX>(m_tiles, a, blocks, st)
                                           : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, EX>(m_tiles, a, blocks, st);
 }
 
-template <bool EX, typename A>
+template <int EX, typename A>
 hipError_t launch_any(int dtype, int layout, uint32_t m_tiles, const A& a, uint64_t blocks, hipStream_t st) {
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
@@ -299,11 +308,13 @@ hipError_t launch_any(int dtype, int layout, uint32_t m_tiles, const A& a, uint6
 
 // rows * a.tiles workgroups (mel_plan_run keeps the product within gridDim.x's 2^31 - 1)
 hipError_t launch_mel(int dtype, int layout, uint32_t m_tiles, const MelArgs& a, uint64_t rows, hipStream_t st) {
-    return launch_any<false>(dtype, layout, m_tiles, a, rows * a.tiles, st);
+    return launch_any<0>(dtype, layout, m_tiles, a, rows * a.tiles, st);
 }
 
-hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, const MelExArgs& e, uint64_t rows, hipStream_t st) {
-    return launch_any<true>(dtype, layout, m_tiles, e, rows * e.a.tiles, st);
+hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, bool framed, const MelExArgs& e, uint64_t rows,
+                         hipStream_t st) {
+    return framed ? launch_any<2>(dtype, layout, m_tiles, e, rows * e.a.tiles, st)
+                  : launch_any<1>(dtype, layout, m_tiles, e, rows * e.a.tiles, st);
 }
 
 // a.total passes of MEL_NORM_CHUNK elements, over at most 2^31 - 1 workgroups

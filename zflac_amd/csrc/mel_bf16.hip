@@ -49,7 +49,11 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-template <int DT, int LAYOUT, int MT, int TERMS>
+// FR: a framed plan (a frame shorter than the DFT or a Kaldi framing). FR = false is the kernel as
+// it was before framed plans, statement for statement: the start offset is the unsigned N / 2 or 0,
+// the reflect bound is half the span and there is no mirror, so the plans that existed compile to
+// the code they had (a shared body cost k_mel_split 1 % on Whisper's shape).
+template <int DT, int LAYOUT, int MT, int TERMS, bool FR>
 __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelSplitArgs sa) {
     using OT = typename Out<DT>::T;
     constexpr uint32_t NP = TERMS == 6 ? 3 : 2;                  // pieces of an operand in use
@@ -62,21 +66,22 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
     const uint64_t row = blockIdx.x / a.tiles;
     const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
     const float* const x = a.wave + row * a.row_stride;
-    const uint32_t N = a.n_fft;
+    const uint32_t N = a.n_fft;  // the frame span: the DFT size, or a framed plan's frame length
     uint64_t n_row = a.wave_frames;
     if (sa.e.lengths) {
         const uint64_t n = sa.e.lengths[row];
         n_row = n < a.wave_frames ? n : a.wave_frames;
     }
-    const bool reflect = sa.e.pad == ZFLAC_PAD_REFLECT;
+    const bool reflect = FR ? sa.e.pad != ZFLAC_PAD_ZEROS : sa.e.pad == ZFLAC_PAD_REFLECT;  // FR: or _MIRROR
+    const int64_t off = FR ? (int64_t)a.off : (int64_t)(uint32_t)a.off;
     // this lane's frame, and sample 8 (l >> 5) of it: where its eight samples of block 0 start
     const uint64_t j = j0 + wv * MEL_TILE + (lane & 31);
     const bool ok = j < a.frames;
     const uint32_t n_lane = 8 * (lane >> 5);
-    const int64_t base = ok ? (int64_t)((a.first_frame + j) * a.hop) - (int64_t)a.off + n_lane : 0;
+    const int64_t base = ok ? (int64_t)((a.first_frame + j) * a.hop) - off + n_lane : 0;
     // interior (uniform): every frame of the tile exists and every sample index the workgroup
     // forms lies in [0, n_row), blocks of padding (n >= N) included: nothing to decide per sample
-    const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - (int64_t)a.off;
+    const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - off;
     const bool interior = N % MEL_BF16_K == 0 && j0 + MEL_FRAMES <= a.frames && lo >= 0 &&
                           (uint64_t)lo + (uint64_t)(MEL_FRAMES - 1) * a.hop + N <= n_row;
 
@@ -86,11 +91,13 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
 #pragma unroll
             for (int i = 0; i < 8; i++) v[i] = x[s0 + i];
         } else if (reflect) {  // x~[s] = x[rho(s)]: one reflection about 0 or n_row - 1, zero beyond it
-            const int64_t nr = (int64_t)n_row, half = (int64_t)(N / 2);
+            // (k_mel_ex's rule: _MIRROR repeats the edge sample, m = 1, and has no bound but the row)
+            const int64_t nr = (int64_t)n_row, m = FR && sa.e.pad == ZFLAC_PAD_MIRROR;
+            const int64_t half = !FR ? (int64_t)(N / 2) : m ? (int64_t)1 << 62 : (int64_t)sa.e.pad_half;
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int64_t s = s0 + i;
-                const int64_t r = s < 0 ? -s : (s >= nr ? 2 * (nr - 1) - s : s);
+                const int64_t r = s < 0 ? -s - m : (s >= nr ? 2 * (nr - 1) + m - s : s);
                 const bool in = ok && kb * MEL_BF16_K + n_lane + i < N && s >= -half && s < nr + half && r >= 0 && r < nr;
                 v[i] = in ? x[r] : 0.0f;
             }
@@ -234,10 +241,10 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
     }
 }
 
-template <int DT, int LAYOUT, int TERMS>
+template <int DT, int LAYOUT, int TERMS, bool FR>
 hipError_t launch_mt(uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
 #define ZFLAC_MEL_LAUNCH(MT) \
-    hipLaunchKernelGGL((k_mel_split<DT, LAYOUT, MT, TERMS>), dim3(blocks), dim3(MEL_THREADS), 0, st, s); \
+    hipLaunchKernelGGL((k_mel_split<DT, LAYOUT, MT, TERMS, FR>), dim3(blocks), dim3(MEL_THREADS), 0, st, s); \
     break
     switch (m_tiles) {
         case 1: ZFLAC_MEL_LAUNCH(1);
@@ -250,18 +257,18 @@ hipError_t launch_mt(uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, h
     return hipGetLastError();
 }
 
-template <int DT, int TERMS>
+template <int DT, int TERMS, bool FR>
 hipError_t launch_layout(int layout, uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
-    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, TERMS>(m_tiles, s, blocks, st)
-                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, TERMS>(m_tiles, s, blocks, st);
+    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, TERMS, FR>(m_tiles, s, blocks, st)
+                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, TERMS, FR>(m_tiles, s, blocks, st);
 }
 
-template <int TERMS>
+template <int TERMS, bool FR>
 hipError_t launch_dt(int dtype, int layout, uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
     switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_layout<ZFLAC_EXPORT_F32, TERMS>(layout, m_tiles, s, blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_layout<ZFLAC_EXPORT_F16, TERMS>(layout, m_tiles, s, blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_layout<ZFLAC_EXPORT_BF16, TERMS>(layout, m_tiles, s, blocks, st);
+        case ZFLAC_EXPORT_F32: return launch_layout<ZFLAC_EXPORT_F32, TERMS, FR>(layout, m_tiles, s, blocks, st);
+        case ZFLAC_EXPORT_F16: return launch_layout<ZFLAC_EXPORT_F16, TERMS, FR>(layout, m_tiles, s, blocks, st);
+        case ZFLAC_EXPORT_BF16: return launch_layout<ZFLAC_EXPORT_BF16, TERMS, FR>(layout, m_tiles, s, blocks, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -269,13 +276,15 @@ hipError_t launch_dt(int dtype, int layout, uint32_t m_tiles, const MelSplitArgs
 }  // namespace
 
 // rows * tiles workgroups, as k_mel (mel_plan_run keeps the product within gridDim.x's 2^31 - 1)
-hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t terms, const MelSplitArgs& s, uint64_t rows,
-                            hipStream_t st) {
+hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t terms, bool framed, const MelSplitArgs& s,
+                            uint64_t rows, hipStream_t st) {
     const uint64_t blocks = rows * s.e.a.tiles;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull || !s.pieces) return hipErrorInvalidValue;
-    if (terms == 6) return launch_dt<6>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
-    if (terms == 3) return launch_dt<3>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
+    if (terms == 6) return framed ? launch_dt<6, true>(dtype, layout, m_tiles, s, (uint32_t)blocks, st)
+                                  : launch_dt<6, false>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
+    if (terms == 3) return framed ? launch_dt<3, true>(dtype, layout, m_tiles, s, (uint32_t)blocks, st)
+                                  : launch_dt<3, false>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
     return hipErrorInvalidValue;
 }
 

@@ -1,5 +1,6 @@
 // mel_host.cpp -- the feature plan (zflac_mel): its tables in device memory, its own stream, and
-// the launches of k_mel, k_mel_ex and k_mel_norm, or of k_mel_split for a split-bf16 plan. A run stages nothing: the tables never change
+// the launches of k_mel, k_mel_ex and k_mel_norm, or of k_mel_split for a split-bf16 plan, and of
+// k_mel_cmvn behind them. A run stages nothing: the tables never change
 // and the arguments go by value, so runs of one plan on different streams may overlap.
 #include "batch.h"
 #include "launch.h"
@@ -18,10 +19,8 @@ struct zflac_mel {
 
 namespace zflac {
 
-int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out) {
-    MelPlan p;
-    const int rc = mel_plan_create_ex(d, math, out, p);  // the arguments first, the device afterwards
-    if (rc) return rc;
+// The tables of a checked plan, then the device
+static int mel_build(const MelPlan& p, const zflac_mel_desc* d, int device, zflac_mel** out) {
     *out = nullptr;
     return guarded([&]() -> int {
         std::vector<float> basis, filt;
@@ -49,6 +48,22 @@ int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** o
     });
 }
 
+int mel_create(const zflac_mel_desc* d, uint32_t math, int device, zflac_mel** out) {
+    MelPlan p;
+    const int rc = mel_plan_create_ex(d, math, out, p);  // the arguments first, the device afterwards
+    if (rc) return rc;
+    return mel_build(p, d, device, out);
+}
+
+int mel_create_framed(const zflac_mel_desc* d, const zflac_mel_frame_desc* f, uint32_t math, int device, zflac_mel** out) {
+    MelPlan p;
+    const int rc = mel_plan_create_framed(d, f, math, out, p);
+    if (rc) return rc;
+    return mel_build(p, d, device, out);
+}
+
+uint64_t mel_plan_frames_of(const zflac_mel* m, uint64_t n_samples) { return m ? mel_plan_frames(m->plan, n_samples) : 0; }
+
 // The launch arguments of a run the planner has accepted
 static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_frames, uint64_t row_stride,
                         uint64_t first_frame, uint64_t frames, void* dst, const MelGrid& g) {
@@ -63,9 +78,11 @@ static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_fra
     a.first_frame = first_frame;
     a.frames = frames;
     a.tiles = g.tiles;
-    a.n_fft = p.n_fft;
+    // the span of the sums: the f32 table's sample rows; a split plan's frame length (its kernel
+    // reads zeros at and past it)
+    a.n_fft = p.math == ZFLAC_MEL_MATH_F32 ? p.span : p.win_length;
     a.hop = p.hop;
-    a.off = p.center ? p.n_fft / 2 : 0;
+    a.off = p.off;
     a.n_bins = p.n_bins;
     a.bin_tiles = p.bin_tiles;
     a.scale = p.scale;
@@ -82,7 +99,7 @@ static hipError_t launch_split(const zflac_mel* m, const MelExArgs& e, uint64_t 
     s.e = e;
     s.pieces = m->pieces.p;
     s.k_blocks = p.k_blocks;
-    return launch_mel_split(p.dtype, p.layout, p.m_tiles, p.math == ZFLAC_MEL_MATH_BF16X6 ? 6 : 3, s, rows, st);
+    return launch_mel_split(p.dtype, p.layout, p.m_tiles, p.math == ZFLAC_MEL_MATH_BF16X6 ? 6 : 3, p.framed(), s, rows, st);
 }
 
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
@@ -97,7 +114,7 @@ int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames
         const MelArgs a = mel_args(m, wave, wave_frames, row_stride, first_frame, frames, dst, g);
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
         if (p.math == ZFLAC_MEL_MATH_F32) ck(launch_mel(p.dtype, p.layout, p.m_tiles, a, rows, st));
-        else ck(launch_split(m, MelExArgs{a, nullptr, nullptr, ZFLAC_PAD_ZEROS}, rows, st));
+        else ck(launch_split(m, MelExArgs{a, nullptr, nullptr, ZFLAC_PAD_ZEROS, p.n_fft / 2}, rows, st));
         if (!stream) ck(hipStreamSynchronize(st));
         return E_OK;
     });
@@ -117,11 +134,12 @@ int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
         e.lengths = r->lengths_device;
         e.row_max = r->row_max_device;
         e.pad = r->pad;
+        e.pad_half = p.n_fft / 2;
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
         if (e.row_max) ck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e.row_max), (int)0xFF800000u, r->rows, st));
         if (p.math != ZFLAC_MEL_MATH_F32) ck(launch_split(m, e, r->rows, st));
         else if (mel_run_is_plain(*r)) ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, r->rows, st));
-        else ck(launch_mel_ex(p.dtype, p.layout, p.m_tiles, e, r->rows, st));
+        else ck(launch_mel_ex(p.dtype, p.layout, p.m_tiles, p.framed(), e, r->rows, st));
         if (r->norm == ZFLAC_NORM_ROW_MAX) {
             MelNormArgs n;
             n.dst = r->dst_device;
@@ -134,6 +152,34 @@ int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
             n.mul = r->mul;
             ck(launch_mel_norm(p.dtype, n, st));
         }
+        if (!stream) ck(hipStreamSynchronize(st));
+        return E_OK;
+    });
+}
+
+// One launch of k_mel_cmvn; nothing is staged from the host
+int mel_cmvn(zflac_mel* m, const zflac_mel_cmvn_desc* c, void* stream) {
+    uint64_t passes = 0;
+    const int rc = mel_plan_cmvn(m ? &m->plan : nullptr, c, passes);
+    if (rc || passes == 0) return rc;
+    return guarded([&]() -> int {
+        DeviceScope scope(m->device);
+        const MelPlan& p = m->plan;
+        MelCmvnArgs a;
+        a.feat = c->feat_device;
+        a.valid = c->valid_device;
+        a.mean = c->mean_device;
+        a.std = c->std_device;
+        a.rows = c->rows;
+        a.frames = c->frames;
+        a.total = passes;
+        a.n_bins = p.n_bins;
+        a.mode = c->mode;
+        a.ddof = c->ddof;
+        a.eps = c->eps;
+        a.pad_value = c->pad_value;
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
+        ck(launch_mel_cmvn(p.dtype, p.layout, a, st));
         if (!stream) ck(hipStreamSynchronize(st));
         return E_OK;
     });

@@ -20,6 +20,10 @@
 //            B operand of one MFMA as it stands, against this A operand.
 //            The filter tiles are m_tiles = 1, 2, 4 or 8 (the least that holds n_bins).
 //
+// A framed plan (zflac_hip_mel_create_framed) sums over the Nw samples of its frame instead of N:
+// the basis has p.span = Nw + (Nw & 1) sample rows (n >= Nw: zeros) and the pieces 16 ceil(Nw / 16),
+// while the bin tiles still follow K = N / 2 + 1 of the DFT size.
+//
 // A split plan (ZFLAC_MEL_MATH_BF16X6 / _BF16X3, k_mel_split) has no f32 basis table. Its first
 // product runs on v_mfma_f32_32x32x16_bf16 (16 terms of the sum per instruction: lane l holds
 // A[row l & 31][k = 8 (l >> 5) + j], j = 0..7, eight bf16 = 16 bytes), over the bf16 pieces
@@ -56,7 +60,16 @@ struct MelPlan {
     uint32_t math = ZFLAC_MEL_MATH_F32;
     uint32_t k_blocks = 0;   // ceil(N / MEL_BF16_K): sample blocks of a split plan
     uint32_t n_pieces = 0;   // bf16 pieces of a basis entry in the table: 3 (BF16X6), 2 (BF16X3), 0 (F32)
-    size_t basis_floats() const { return (size_t)bin_tiles * n_fft * 2 * MEL_TILE; }
+    // The frame (zflac_hip_mel_create_framed; n_fft, STFT, the centring offset and no operator otherwise)
+    uint32_t win_length = 0; // Nw: samples of a frame
+    uint32_t span = 0;       // sample rows of the f32 basis table: Nw, or Nw + 1 (a zero row) when Nw is odd
+    int32_t off = 0;         // frame t starts at sample t * hop - off
+    uint8_t framing = ZFLAC_FRAMING_STFT, remove_dc = 0;
+    float preemphasis = 0, sample_scale = 1;
+    // whether the kernels need what framed plans added (a frame that is not the DFT's, a Kaldi
+    // framing); a folded operator alone does not: such a plan runs the kernels as they were
+    bool framed() const { return win_length != n_fft || framing != ZFLAC_FRAMING_STFT; }
+    size_t basis_floats() const { return (size_t)bin_tiles * span * 2 * MEL_TILE; }
     size_t piece_elems() const { return (size_t)bin_tiles * k_blocks * 2 * n_pieces * MEL_BF16_OPERAND; }
     size_t filter_floats() const { return (size_t)bin_tiles * 16 * m_tiles * 64; }
     size_t elem_size() const { return dtype == ZFLAC_EXPORT_F32 ? 4 : 2; }
@@ -71,11 +84,22 @@ constexpr uint32_t mel_acc_row(uint32_t r) { return (r & 3) + 8 * (r >> 2); }
 int mel_plan_create(const zflac_mel_desc* d, const void* out_ptr, MelPlan& p);
 // zflac_hip_mel_create_ex's: everything above, in that order, then math (a known ZFLAC_MEL_MATH_*)
 int mel_plan_create_ex(const zflac_mel_desc* d, uint32_t math, const void* out_ptr, MelPlan& p);
+// zflac_hip_mel_create_framed's, in this order: mel_plan_create's up to and including floor; f,
+// size, win_length, framing, remove_dc, preemphasis, sample_scale, reserved; window (Nw floats) and
+// filters (NULL, then every value finite); framing against center; hop <= Nw; math
+int mel_plan_create_framed(const zflac_mel_desc* d, const zflac_mel_frame_desc* f, uint32_t math, const void* out_ptr,
+                           MelPlan& p);
 
 // Where the kernel's tables hold c[n][k] (im = 0) or s[n][k] (im = 1), and filters[m][k]
 size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im);
 size_t mel_filter_index(const MelPlan& p, uint32_t m, uint32_t k);
-// Both tables, p.basis_floats() and p.filter_floats() long, zero wherever no (n, k) or (m, k) lands
+// Both tables, p.basis_floats() and p.filter_floats() long, zero wherever no (n, k) or (m, k) lands.
+// A framed plan's c and s are the folded c' and s' of include/zflac_hip.h: column k of the window
+// times the DFT row, u[m] (double), taken through the transpose of the frame operator in O(Nw):
+//   v[0] = (1 - a) u[0] - a u[1];  v[n] = u[n] - a u[n + 1], 0 < n < Nw - 1;  v[Nw - 1] = u[Nw - 1]
+//   (Nw = 1: v[0] = (1 - a) u[0]);  v -= mean(v) if remove_dc;  v *= g;  rounded to f32 once.
+// Each step is skipped when it is the identity (a = 0, no DC removal, g = 1), so such a plan's
+// tables are mel_create_ex's byte for byte.
 void mel_tables(const MelPlan& p, const float* window, const float* filters, std::vector<float>& basis,
                 std::vector<float>& filt);
 
@@ -105,7 +129,8 @@ int mel_plan_run(const MelPlan* p, uintptr_t wave, uint64_t rows, uint64_t wave_
 // zflac_hip_mel_run_ex's checks, in this order: p (the plan, NULL = no plan) and r; size; pad, then
 // norm (known values); reserved, then reserved2; everything mel_plan_run checks, in its order, on
 // the fields of the same names (its arithmetic: this calls it); lengths_device's alignment (8);
-// row_max_device's alignment (4); ZFLAC_PAD_REFLECT with an uncentred plan; ZFLAC_NORM_ROW_MAX:
+// row_max_device's alignment (4); ZFLAC_PAD_REFLECT with an uncentred plan, then ZFLAC_PAD_MIRROR
+// with a plan that is not ZFLAC_FRAMING_KALDI_CENTER; ZFLAC_NORM_ROW_MAX:
 // row_max_device, a log scale, range (finite, >= 0), add (finite), mul (finite, != 0);
 // ZFLAC_NORM_NONE: range, add, mul all 0. g is mel_plan_run's; rows == 0 is E_OK with
 // g.blocks == 0 once every check has passed (none of the added ones involves rows).
@@ -114,5 +139,13 @@ int mel_plan_run_ex(const MelPlan* p, const zflac_mel_run_desc* r, MelGrid& g);
 bool mel_run_is_plain(const zflac_mel_run_desc& r);
 
 uint64_t mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, int center);
+// zflac_hip_mel_plan_frames: the frame count of the plan's framing
+uint64_t mel_plan_frames(const MelPlan& p, uint64_t n_samples);
+
+// zflac_hip_mel_cmvn's checks, in this order: p and c; size; mode; ddof; reserved; feat_device;
+// frames; the tensor's bytes (63 bits); valid_device's alignment (8), mean_device's and
+// std_device's (4); eps (finite, >= 0); pad_value (finite). passes: workgroup passes of k_mel_cmvn
+// (rows * n_bins bins first, rows frames first); rows == 0 is E_OK with passes == 0.
+int mel_plan_cmvn(const MelPlan* p, const zflac_mel_cmvn_desc* c, uint64_t& passes);
 
 }  // namespace zflac

@@ -312,9 +312,70 @@ def mel_filters(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None, mel_scale="sl
     return w.astype(np.float32)
 
 
+def kaldi_window(name, win_length):
+    """Kaldi's frame windows -> numpy float32 [win_length], with c[n] = cos(2 pi n / (win_length - 1)):
+      "povey"        (0.5 - 0.5 c[n]) ** 0.85
+      "hanning"      0.5 - 0.5 c[n]
+      "hamming"      0.54 - 0.46 c[n]
+      "rectangular"  1
+    (symmetric windows: the first and last samples of "hanning" and "povey" are 0). Computed in
+    float64 and rounded once; win_length = 1 gives [1] for every name."""
+    import numpy as np
+
+    nw = int(win_length)
+    if nw < 1:
+        raise ValueError("win_length >= 1")
+    if name not in ("povey", "hanning", "hamming", "rectangular"):
+        raise ValueError("window is 'povey', 'hanning', 'hamming' or 'rectangular'")
+    if nw == 1 or name == "rectangular":
+        return np.ones(nw, dtype=np.float32)
+    c = np.cos(2.0 * np.pi * np.arange(nw, dtype=np.float64) / (nw - 1))
+    if name == "hamming":
+        return (0.54 - 0.46 * c).astype(np.float32)
+    h = np.maximum(0.5 - 0.5 * c, 0.0)
+    return (h ** 0.85 if name == "povey" else h).astype(np.float32)
+
+
+def kaldi_mel_filters(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
+    """Kaldi's mel filterbank (triangles in the mel domain, no VTLN) -> numpy float32
+    [n_mels, n_fft // 2 + 1]. mel(f) = 1127 ln(1 + f / 700); a high_freq <= 0 is added to the
+    Nyquist frequency. With D = (mel(high) - mel(low)) / (n_mels + 1), filter m has left =
+    mel(low) + m D, centre = left + D, right = centre + D; bin k < n_fft / 2 at mel_k =
+    mel(k sample_rate / n_fft) strictly inside (left, right) weighs (mel_k - left) / D up to the
+    centre and (right - mel_k) / D beyond it. The Nyquist column is 0 (Kaldi has n_fft / 2 bins).
+    Computed in float64 and rounded once."""
+    import numpy as np
+
+    n_fft, n_mels = int(n_fft), int(n_mels)
+    if n_fft < 2 or n_fft % 2 or n_mels < 1:
+        raise ValueError("n_fft even and >= 2, n_mels >= 1")
+    nyquist = 0.5 * float(sample_rate)
+    low, high = float(low_freq), float(high_freq)
+    if high <= 0.0:
+        high += nyquist
+    if not (0.0 <= low < high <= nyquist):
+        raise ValueError("0 <= low_freq < high_freq <= sample_rate / 2")
+
+    def mel(f):
+        return 1127.0 * np.log(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+    mel_lo, mel_hi = mel(low), mel(high)
+    delta = (mel_hi - mel_lo) / (n_mels + 1)
+    left = (mel_lo + np.arange(n_mels, dtype=np.float64) * delta)[:, None]
+    centre, right = left + delta, left + 2.0 * delta
+    mk = mel(np.arange(n_fft // 2, dtype=np.float64) * (float(sample_rate) / n_fft))[None, :]
+    w = np.where(mk <= centre, (mk - left) / delta, (right - mk) / delta)
+    w = np.where((mk > left) & (mk < right), w, 0.0)
+    out = np.zeros((n_mels, n_fft // 2 + 1), dtype=np.float32)
+    out[:, :n_fft // 2] = w.astype(np.float32)
+    return out
+
+
 _MEL_SCALES = {"power": _lib.MEL_POWER, "log10": _lib.MEL_LOG10, "ln": _lib.MEL_LN}
 _MEL_LAYOUTS = {"bins_first": _lib.MEL_BINS_FIRST, "frames_first": _lib.MEL_FRAMES_FIRST}
-_MEL_PADS = {"zeros": _lib.PAD_ZEROS, "reflect": _lib.PAD_REFLECT}
+_MEL_PADS = {"zeros": _lib.PAD_ZEROS, "reflect": _lib.PAD_REFLECT, "mirror": _lib.PAD_MIRROR}
+_MEL_FRAMINGS = {"stft": _lib.FRAMING_STFT, "snip": _lib.FRAMING_SNIP, "kaldi_center": _lib.FRAMING_KALDI_CENTER}
+_MEL_CMVN = {"mean": _lib.CMVN_MEAN, "mean_var": _lib.CMVN_MEAN_VAR}
 _MEL_MATHS = {"f32": _lib.MEL_MATH_F32, "bf16x6": _lib.MEL_MATH_BF16X6, "bf16x3": _lib.MEL_MATH_BF16X3}
 
 
@@ -349,6 +410,23 @@ class MelSpectrogram:
     within 3 * 2^-24 (f32-grade) or 2^-14 (about 84 dB) of sum |c| |x| of the full product; a bin
     further than that below its frame's loudest content is noise under "bf16x3". mel.math reads
     the plan's mode back from the library.
+
+    Framed plans (zflac_hip_mel_create_framed; with every argument below at its default the plan is
+    zflac_hip_mel_create_ex's, as before). win_length: the frame length Nw <= n_fft, the frame
+    zero-extended to the n_fft-point DFT; `window` then has Nw values ("hann": periodic over Nw; or
+    a kaldi_window name). framing: "stft" (torch.stft with the window centred in the DFT), "snip"
+    (Kaldi, snip_edges=True: frame t at t hop, (n - Nw) // hop + 1 frames) or "kaldi_center"
+    (snip_edges=False: frame t at t hop + hop // 2 - Nw // 2, (n + hop // 2) // hop frames); the
+    Kaldi framings need center=False, and all need hop <= Nw. Per frame, in Kaldi's order:
+    sample_scale (32768 takes [-1, 1) to Kaldi's 16-bit scale), remove_dc (subtract the frame's
+    mean), preemphasis a (y[0] = (1 - a) f[0], y[n] = f[n] - a f[n - 1]), the window. All of it is
+    folded into the plan's tables and costs nothing per run. pad="mirror" ("kaldi_center" only)
+    mirrors a row about its ends with the edge sample repeated, as Kaldi does.
+    cmvn: None, "mean" or "mean_var": behind the features, every (row, bin) is normalised over the
+    row's feature_lengths valid frames (zflac_hip_mel_cmvn, k_mel_cmvn): (x - mean) / (std + cmvn_eps),
+    std with cmvn_ddof 0 or 1, frames past the valid ones set to cmvn_pad. The statistics of the
+    last call are mel.last_mean and mel.last_std ([B, (C,) n_bins] float32).
+    Not provided: dither, use_energy / raw_energy, VTLN, pre-emphasis over the whole waveform.
     The object owns a plan of the library: close() it, or use it in `with`."""
 
     @classmethod
@@ -361,9 +439,32 @@ class MelSpectrogram:
         return cls(16000, 400, 160, n_mels, scale="log10", floor=1e-10, center=True, dtype=dtype, device=device,
                    pad="reflect", normalize=(8.0, 4.0, 0.25), reflect_at="end", math=math)
 
+    @classmethod
+    def kaldi_fbank(cls, sample_rate=16000, num_mel_bins=80, frame_length_ms=25.0, frame_shift_ms=10.0, snip_edges=True,
+                    preemphasis=0.97, remove_dc=True, window="povey", low_freq=20.0, high_freq=0.0, math="f32",
+                    dtype=torch.float32, cmvn=None, device=0, **cmvn_kw):
+        """Kaldi's compute-fbank-feats (kaldifeat, torchaudio.compliance.kaldi.fbank, lhotse) for
+        waveforms in [-1, 1): frames of frame_length_ms every frame_shift_ms in the next power-of-two
+        DFT, the samples scaled by 32768, DC removal, pre-emphasis and the window per frame,
+        kaldi_mel_filters, ln with the floor 2^-23 (FLT_EPSILON), [B, (C,) frames, num_mel_bins].
+        snip_edges=False centres the frames and mirrors the row's ends. Dither is 0; use_energy,
+        raw_energy and VTLN are not provided."""
+        nw = int(sample_rate * frame_length_ms / 1000.0)
+        hop = int(sample_rate * frame_shift_ms / 1000.0)
+        n_fft = 2
+        while n_fft < nw:
+            n_fft *= 2
+        return cls(sample_rate, n_fft, hop, num_mel_bins, window=window,
+                   filters=kaldi_mel_filters(sample_rate, n_fft, num_mel_bins, low_freq, high_freq), scale="ln",
+                   floor=2.0 ** -23, center=False, dtype=dtype, layout="frames_first", device=device,
+                   pad="zeros" if snip_edges else "mirror", math=math, win_length=nw,
+                   framing="snip" if snip_edges else "kaldi_center", remove_dc=remove_dc, preemphasis=preemphasis,
+                   sample_scale=32768.0, cmvn=cmvn, **cmvn_kw)
+
     def __init__(self, sample_rate, n_fft=400, hop=160, n_mels=80, window="hann", filters=None, scale="log10",
                  floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, pad="zeros",
-                 normalize=None, reflect_at="length", math="f32", **filter_kw):
+                 normalize=None, reflect_at="length", math="f32", win_length=None, framing="stft", remove_dc=False,
+                 preemphasis=0.0, sample_scale=1.0, cmvn=None, cmvn_eps=1e-5, cmvn_ddof=0, cmvn_pad=0.0, **filter_kw):
         import math as _math
 
         import numpy as np
@@ -372,9 +473,27 @@ class MelSpectrogram:
             raise ValueError("math is 'f32', 'bf16x6' or 'bf16x3'")
         check_single_runtime()
         if pad not in _MEL_PADS:
-            raise ValueError("pad is 'zeros' or 'reflect'")
+            raise ValueError("pad is 'zeros', 'reflect' or 'mirror'")
         if pad == "reflect" and not center:
             raise ValueError("pad='reflect' needs center=True")
+        if framing not in _MEL_FRAMINGS:
+            raise ValueError("framing is 'stft', 'snip' or 'kaldi_center'")
+        if framing != "stft" and center:
+            raise ValueError(f"framing={framing!r} needs center=False")
+        if pad == "mirror" and framing != "kaldi_center":
+            raise ValueError("pad='mirror' needs framing='kaldi_center'")
+        preemphasis, sample_scale = float(preemphasis), float(sample_scale)
+        if not (_math.isfinite(preemphasis) and 0.0 <= preemphasis <= 1.0):
+            raise ValueError("0 <= preemphasis <= 1")
+        if not (_math.isfinite(sample_scale) and 2.0 ** -64 <= abs(sample_scale) <= 2.0 ** 64):
+            raise ValueError("2^-64 <= |sample_scale| <= 2^64")
+        if cmvn is not None and cmvn not in _MEL_CMVN:
+            raise ValueError("cmvn is None, 'mean' or 'mean_var'")
+        cmvn_eps, cmvn_pad = float(cmvn_eps), float(cmvn_pad)
+        if not (_math.isfinite(cmvn_eps) and cmvn_eps >= 0.0) or not _math.isfinite(cmvn_pad) or cmvn_ddof not in (0, 1):
+            raise ValueError("cmvn_eps finite and >= 0, cmvn_pad finite, cmvn_ddof 0 or 1")
+        self.cmvn, self.cmvn_eps, self.cmvn_ddof, self.cmvn_pad = cmvn, cmvn_eps, int(cmvn_ddof), cmvn_pad
+        self.last_mean = self.last_std = None
         if reflect_at not in ("length", "end"):
             raise ValueError("reflect_at is 'length' or 'end'")
         if normalize is not None:
@@ -395,15 +514,24 @@ class MelSpectrogram:
         n_fft, hop = int(n_fft), int(hop)
         if not (2 <= n_fft <= 2048 and n_fft % 2 == 0 and 1 <= hop <= n_fft):
             raise ValueError("n_fft even in 2..2048, 1 <= hop <= n_fft")
+        nw = n_fft if win_length is None else int(win_length)
+        if not 1 <= nw <= n_fft:
+            raise ValueError("1 <= win_length <= n_fft")
+        self.framed = nw != n_fft or framing != "stft" or bool(remove_dc) or preemphasis != 0.0 or sample_scale != 1.0
+        if self.framed and hop > nw:
+            raise ValueError("hop <= win_length")
         if isinstance(window, str):
-            if window != "hann":
-                raise ValueError("window is 'hann' or an array of n_fft values")
-            w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft)).astype(np.float32)
+            if window == "hann":
+                w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nw, dtype=np.float64) / nw)).astype(np.float32)
+            elif window in ("povey", "hanning", "hamming", "rectangular"):
+                w = kaldi_window(window, nw)
+            else:
+                raise ValueError("window is 'hann', a kaldi_window name or an array of win_length values")
         else:
             w = np.ascontiguousarray(window.detach().cpu().numpy() if isinstance(window, torch.Tensor) else window,
                                      dtype=np.float32)
-        if w.shape != (n_fft,):
-            raise ValueError(f"window has shape {w.shape}, expected {(n_fft,)}")
+        if w.shape != (nw,):
+            raise ValueError(f"window has shape {w.shape}, expected {(nw,)}")
         if filters is None:
             fb = mel_filters(sample_rate, n_fft, n_mels, **filter_kw)
         else:
@@ -417,12 +545,20 @@ class MelSpectrogram:
         self.center, self.dtype, self.layout, self.scale, self.device = bool(center), dtype, layout, scale, int(device)
         self.floor = 0.0 if scale == "power" else float(floor)
         self.window, self.filters = w, fb
+        self.win_length, self.framing, self.remove_dc = nw, framing, bool(remove_dc)
+        self.preemphasis, self.sample_scale = preemphasis, sample_scale
         self._L = _lib.load()
         desc = _lib.zflac_mel_desc(ctypes.sizeof(_lib.zflac_mel_desc), _DTYPES[dtype], _MEL_LAYOUTS[layout],
                                    _MEL_SCALES[scale], int(self.center), n_fft, hop, self.n_bins, 0, self.floor,
                                    w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                    fb.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         self._h = ctypes.c_void_p()
+        if self.framed:
+            fd = _lib.zflac_mel_frame_desc(ctypes.sizeof(_lib.zflac_mel_frame_desc), nw, _MEL_FRAMINGS[framing],
+                                           int(self.remove_dc), preemphasis, sample_scale, 0)
+            errors.check(self._L.zflac_hip_mel_create_framed(ctypes.byref(desc), ctypes.byref(fd), _MEL_MATHS[math],
+                                                             self.device, ctypes.byref(self._h)), "mel_create_framed")
+            return
         errors.check(self._L.zflac_hip_mel_create_ex(ctypes.byref(desc), _MEL_MATHS[math], self.device,
                                                      ctypes.byref(self._h)), "mel_create_ex")
 
@@ -433,13 +569,20 @@ class MelSpectrogram:
         return next(k for k, v in _MEL_MATHS.items() if v == code)
 
     def mel_frames(self, n_samples):
-        """Frames of a row of n_samples (zflac_hip_mel_frames): an int, or a tensor for a tensor."""
+        """Frames of a row of n_samples under the plan's framing (zflac_hip_mel_plan_frames): an
+        int, or a tensor for a tensor."""
         if isinstance(n_samples, torch.Tensor):
             n = n_samples.to(torch.int64)
+            if self.framing == "snip":
+                return torch.where(n >= self.win_length, (n - self.win_length) // self.hop + 1, torch.zeros_like(n))
+            if self.framing == "kaldi_center":
+                return (n + self.hop // 2) // self.hop
             if self.center:
                 return torch.where(n > 0, n // self.hop + 1, torch.zeros_like(n))
             return torch.where(n >= self.n_fft, (n - self.n_fft) // self.hop + 1, torch.zeros_like(n))
-        return int(self._L.zflac_hip_mel_frames(int(n_samples), self.n_fft, self.hop, int(self.center)))
+        if self._h is None:
+            raise ValueError("the plan is closed")
+        return int(self._L.zflac_hip_mel_plan_frames(self._h, int(n_samples)))
 
     def __call__(self, x, lengths=None, frames=None, first_frame=0, out=None, stream=None, return_row_max=False):
         """x: contiguous float32 [B, T] or [B, C, T] on cuda:<device>; lengths: valid samples per
@@ -492,6 +635,7 @@ class MelSpectrogram:
         ex = self.pad != "zeros" or self.normalize is not None or return_row_max
         row_max = torch.empty(lead, dtype=torch.float32, device=dev) if ex else None
         self.last_row_max = row_max
+        self.last_mean = self.last_std = None
         if rows == 0:
             return (out, feature_lengths, row_max) if return_row_max else (out, feature_lengths)
         if stream is None:
@@ -502,6 +646,7 @@ class MelSpectrogram:
             rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, out.data_ptr(),
                                            out.numel() * out.element_size(), stream.cuda_stream or None)
             errors.check(rc, "mel_run")
+            self._cmvn(out, lead, rows, frames, feature_lengths, stream)
             return out, feature_lengths
         per_row = None
         if self.reflect_at == "length":  # one length per row of the launch: [B, C, T] has C rows per entry
@@ -517,7 +662,26 @@ class MelSpectrogram:
         for t in (per_row, row_max):
             if t is not None and stream.cuda_stream:
                 t.record_stream(stream)
+        self._cmvn(out, lead, rows, frames, feature_lengths, stream)
         return (out, feature_lengths, row_max) if return_row_max else (out, feature_lengths)
+
+    def _cmvn(self, out, lead, rows, frames, feature_lengths, stream):
+        """zflac_hip_mel_cmvn over the features just enqueued, feature_lengths as the valid frames."""
+        if self.cmvn is None:
+            return
+        dev = out.device
+        valid = feature_lengths.repeat_interleave(rows // int(feature_lengths.shape[0])).contiguous()
+        mean = torch.empty(lead + (self.n_bins,), dtype=torch.float32, device=dev)
+        std = torch.empty_like(mean)
+        d = _lib.zflac_mel_cmvn_desc(ctypes.sizeof(_lib.zflac_mel_cmvn_desc), _MEL_CMVN[self.cmvn], self.cmvn_ddof, 0,
+                                     out.data_ptr(), rows, frames, valid.data_ptr(), mean.data_ptr(), std.data_ptr(),
+                                     self.cmvn_eps, self.cmvn_pad)
+        errors.check(self._L.zflac_hip_mel_cmvn(self._h, ctypes.byref(d), stream.cuda_stream or None), "mel_cmvn")
+        self._keep_cmvn = valid  # as _keep: read by the launch
+        for t in (valid, mean, std):
+            if stream.cuda_stream:
+                t.record_stream(stream)
+        self.last_mean, self.last_std = mean, std
 
     def close(self):
         if getattr(self, "_h", None) is not None:
