@@ -15,6 +15,7 @@ starts one variant later in every iteration, so that no variant always runs behi
     kaldi_f32 / _bf16x6 / _bf16x3   zflac_hip_mel_run of MelSpectrogram.kaldi_fbank()'s plan: 512-point DFT,
                           400-sample frames every 160, snip framing, DC removal, pre-emphasis 0.97,
                           the povey window, x 32768, 80 Kaldi mel bins, ln, frames first
+    kaldi_*_base          the three kaldi_* legs on --baseline-lib, where it has framed plans
     padded_f32 / _bf16x6 / _bf16x3  the same filters through a plan of zflac_hip_mel_create_ex with the window
                           zero-padded to 512 (no DC removal or pre-emphasis: it cannot express
                           them): what the first product costs over 512 samples instead of 400
@@ -58,9 +59,11 @@ MATHS = (("f32", _lib.MEL_MATH_F32), ("bf16x6", _lib.MEL_MATH_BF16X6), ("bf16x3"
 def baseline_library(path):
     """The entry points of an older build that this tool needs (it lacks the newer ones)."""
     lib = ctypes.CDLL(path)
-    for name in ("zflac_hip_mel_create_ex", "zflac_hip_mel_run", "zflac_hip_mel_run_ex", "zflac_hip_mel_destroy",
-                 "zflac_hip_build_id"):
-        fn = getattr(lib, name)
+    for name in ("zflac_hip_mel_create_ex", "zflac_hip_mel_create_framed", "zflac_hip_mel_run", "zflac_hip_mel_run_ex",
+                 "zflac_hip_mel_destroy", "zflac_hip_build_id"):
+        fn = getattr(lib, name, None)
+        if fn is None:
+            continue
         if name == "zflac_hip_build_id":
             fn.restype, fn.argtypes = ctypes.c_char_p, []
         else:
@@ -122,6 +125,12 @@ def main():
             base_plans[name] = ctypes.c_void_p()
             errors.check(base.zflac_hip_mel_create_ex(ctypes.byref(wd), math, 0, ctypes.byref(base_plans[name])),
                          "baseline mel_create_ex")
+    base_kaldi = {}  # the framed plans of the baseline build, where it has them
+    if base is not None and hasattr(base, "zflac_hip_mel_create_framed"):
+        for name, math in MATHS:
+            base_kaldi[name] = ctypes.c_void_p()
+            errors.check(base.zflac_hip_mel_create_framed(ctypes.byref(kd), ctypes.byref(fd), math, 0,
+                                                          ctypes.byref(base_kaldi[name])), "baseline mel_create_framed")
 
     side = torch.cuda.Stream(dev)
     kframes = int(L.zflac_hip_mel_plan_frames(kaldi["f32"], T))
@@ -190,6 +199,8 @@ def main():
 
     variants = {}
     for name, _ in MATHS:
+        if name in base_kaldi:
+            variants[f"kaldi_{name}_base"] = run_of(base, base_kaldi[name], kout, kframes)
         variants["kaldi_" + name] = run_of(L, kaldi[name], kout, kframes)
         variants["padded_" + name] = run_of(L, padded[name], kout[:, :pframes].contiguous() if pframes != kframes else kout, pframes)
     if base is not None:
@@ -252,9 +263,10 @@ def main():
     for name, _ in MATHS:
         res[f"kaldi_over_padded_{name}"] = res["kaldi_" + name]["median_ms"] / res["padded_" + name]["median_ms"]
     if base is not None:
-        for new, old in (("whisper_f32", "whisper_baseline"), ("whisper_bf16x6", "whisper_bf16x6_base"),
+        for new, old in [("whisper_f32", "whisper_baseline"), ("whisper_bf16x6", "whisper_bf16x6_base"),
                          ("whisper_reflect_f32", "whisper_reflect_f32_base"),
-                         ("whisper_reflect_bf16x6", "whisper_reflect_bf16x6_base")):
+                         ("whisper_reflect_bf16x6", "whisper_reflect_bf16x6_base")] + [
+                             (f"kaldi_{name}", f"kaldi_{name}_base") for name in base_kaldi]:
             res[new + "_median_within_baseline_range"] = res[old]["min_ms"] <= res[new]["median_ms"] <= res[old]["max_ms"]
             res[new + "_median_not_above_baseline_max"] = res[new]["median_ms"] <= res[old]["max_ms"]
     if "torch_fbank" in res:
@@ -263,7 +275,7 @@ def main():
     res["torch_cmvn_over_cmvn_bins_first"] = res["torch_cmvn_bins_first"]["median_ms"] / res["cmvn_bins_first"]["median_ms"]
     for h in list(kaldi.values()) + list(padded.values()) + list(whisper.values()) + [bins_first]:
         L.zflac_hip_mel_destroy(h)
-    for h in base_plans.values():
+    for h in list(base_plans.values()) + list(base_kaldi.values()):
         base.zflac_hip_mel_destroy(h)
     if a.out != "-":
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

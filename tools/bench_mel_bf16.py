@@ -13,6 +13,8 @@ iteration times each variant once, in turn, with torch CUDA events on one side s
 points are called through ctypes directly (no tensor allocation inside an interval):
 
     run_baseline          zflac_hip_mel_run of --baseline-lib (a build of the parent commit), if given
+    *_baseline            the bf16x6, bf16x3 and bf16x6_reflect_row_max legs below on --baseline-lib, where
+                          it has split plans
     f32                   zflac_hip_mel_run of a ZFLAC_MEL_MATH_F32 plan of this build (k_mel)
     bf16x6                ... of a ZFLAC_MEL_MATH_BF16X6 plan (k_mel_split, six piece products)
     bf16x3                ... of a ZFLAC_MEL_MATH_BF16X3 plan (three)
@@ -46,10 +48,13 @@ MFMA_FLOOR_MS = {"bf16x6": 1.25, "bf16x3": 0.81}
 
 
 def baseline_library(path):
-    """The entry points of an older build that this tool needs (it lacks the newer ones)."""
+    """The entry points of an older build that this tool needs; the split plans' where it has them."""
     lib = ctypes.CDLL(path)
-    for name in ("zflac_hip_mel_create", "zflac_hip_mel_run", "zflac_hip_mel_destroy", "zflac_hip_build_id"):
-        fn = getattr(lib, name)
+    for name in ("zflac_hip_mel_create", "zflac_hip_mel_create_ex", "zflac_hip_mel_run", "zflac_hip_mel_run_ex",
+                 "zflac_hip_mel_destroy", "zflac_hip_build_id"):
+        fn = getattr(lib, name, None)
+        if fn is None:
+            continue
         if name == "zflac_hip_build_id":
             fn.restype, fn.argtypes = ctypes.c_char_p, []
         else:
@@ -86,6 +91,12 @@ def main():
     if a.baseline_lib:
         base = baseline_library(a.baseline_lib)
         errors.check(base.zflac_hip_mel_create(ctypes.byref(d), 0, ctypes.byref(base_plan)), "baseline mel_create")
+    base_split = {}  # k_mel_split of the baseline build, where it has split plans
+    if base is not None and hasattr(base, "zflac_hip_mel_create_ex") and hasattr(base, "zflac_hip_mel_run_ex"):
+        for name, math in (("bf16x6", _lib.MEL_MATH_BF16X6), ("bf16x3", _lib.MEL_MATH_BF16X3)):
+            base_split[name] = ctypes.c_void_p()
+            errors.check(base.zflac_hip_mel_create_ex(ctypes.byref(d), math, 0, ctypes.byref(base_split[name])),
+                         "baseline mel_create_ex")
 
     side = torch.cuda.Stream(dev)
     frames = int(L.zflac_hip_mel_frames(T, N, hop, 1))
@@ -104,7 +115,8 @@ def main():
             assert rc == 0, rc
         return fn
 
-    def ex_of(handle, with_norm):
+    def ex_of(handle, with_norm, lib=None):
+        lib = lib or L
         r, ad, mu = norm if with_norm else (0.0, 0.0, 0.0)
         desc = _lib.zflac_mel_run_desc(ctypes.sizeof(_lib.zflac_mel_run_desc), _lib.PAD_REFLECT,
                                        _lib.NORM_ROW_MAX if with_norm else _lib.NORM_NONE, 0, x.data_ptr(), rows, T, T, None, 0,
@@ -112,7 +124,7 @@ def main():
                                        ad, mu, 0)
 
         def fn():
-            rc = L.zflac_hip_mel_run_ex(handle, ctypes.byref(desc), st)
+            rc = lib.zflac_hip_mel_run_ex(handle, ctypes.byref(desc), st)
             assert rc == 0, rc
         return fn
 
@@ -128,7 +140,11 @@ def main():
     if base is not None:
         variants["run_baseline"] = run_of(base, base_plan)
     for name in plans:
+        if name in base_split:
+            variants[name + "_baseline"] = run_of(base, base_split[name])
         variants[name] = run_of(L, plans[name])
+    if base_split:
+        variants["bf16x6_reflect_row_max_baseline"] = ex_of(base_split["bf16x6"], True, base)
     variants["bf16x6_reflect_row_max"] = ex_of(plans["bf16x6"], True)
 
     def timed(fn):
@@ -183,12 +199,18 @@ def main():
         res["f32_median_within_baseline_spread"] = n["median_ms"] <= b["max_ms"]
         if "bf16x6" in res:
             res["bf16x6_range_below_baseline_range"] = res["bf16x6"]["max_ms"] < b["min_ms"]
+    for name in ("bf16x6", "bf16x3", "bf16x6_reflect_row_max"):
+        if name in res and name + "_baseline" in res:
+            b, n = res[name + "_baseline"], res[name]
+            res[name + "_median_within_baseline_range"] = b["min_ms"] <= n["median_ms"] <= b["max_ms"]
     if "bf16x6" in res and "bf16x3" in res:
         res["bf16x3_median_not_above_bf16x6"] = res["bf16x3"]["median_ms"] <= res["bf16x6"]["median_ms"]
     for h in plans.values():
         L.zflac_hip_mel_destroy(h)
     if base is not None:
         base.zflac_hip_mel_destroy(base_plan)
+    for h in base_split.values():
+        base.zflac_hip_mel_destroy(h)
     if a.out != "-":
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

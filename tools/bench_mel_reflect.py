@@ -12,6 +12,7 @@ once, in turn, with torch CUDA events on one side stream; the C entry points are
 ctypes directly (no tensor allocation inside an interval):
 
     run_baseline        zflac_hip_mel_run of --baseline-lib (a build of the parent commit), if given
+    ex_*_baseline       the three ex_reflect* legs below on --baseline-lib, where it has zflac_hip_mel_run_ex
     run                 zflac_hip_mel_run of this build
     ex_default          zflac_hip_mel_run_ex, the all-default descriptor (the same kernel as run)
     ex_zeros_lengths    ... ZFLAC_PAD_ZEROS with lengths_device, every length T: k_mel_ex with no edge tile
@@ -43,10 +44,13 @@ from zflac_amd import _lib, errors, tensor  # noqa: E402
 
 
 def baseline_library(path):
-    """The three entry points of an older build that this tool needs (it may lack the newer ones)."""
+    """The entry points of an older build that this tool needs; zflac_hip_mel_run_ex where it has it."""
     lib = ctypes.CDLL(path)
-    for name in ("zflac_hip_mel_create", "zflac_hip_mel_run", "zflac_hip_mel_destroy", "zflac_hip_build_id"):
-        fn = getattr(lib, name)
+    for name in ("zflac_hip_mel_create", "zflac_hip_mel_run", "zflac_hip_mel_run_ex", "zflac_hip_mel_destroy",
+                 "zflac_hip_build_id"):
+        fn = getattr(lib, name, None)
+        if fn is None:
+            continue
         if name == "zflac_hip_build_id":
             fn.restype, fn.argtypes = ctypes.c_char_p, []
         else:
@@ -100,7 +104,8 @@ def main():
             assert rc == 0, rc
         return fn
 
-    def ex_of(pad, lengths, with_norm):
+    def ex_of(pad, lengths, with_norm, lib=None, handle=None):
+        lib, handle = lib or L, handle or plan
         r, ad, mu = norm if with_norm else (0.0, 0.0, 0.0)
         desc = _lib.zflac_mel_run_desc(ctypes.sizeof(_lib.zflac_mel_run_desc), pad,
                                        _lib.NORM_ROW_MAX if with_norm else _lib.NORM_NONE, 0, x.data_ptr(), rows, T, T,
@@ -108,7 +113,7 @@ def main():
                                        out.numel() * 4, row_max.data_ptr() if with_norm else None, r, ad, mu, 0)
 
         def fn():
-            rc = L.zflac_hip_mel_run_ex(plan, ctypes.byref(desc), st)
+            rc = lib.zflac_hip_mel_run_ex(handle, ctypes.byref(desc), st)
             assert rc == 0, rc
         return fn
 
@@ -129,6 +134,11 @@ def main():
     variants["ex_reflect"] = ex_of(_lib.PAD_REFLECT, None, False)
     variants["ex_reflect_lengths"] = ex_of(_lib.PAD_REFLECT, lengths, False)
     variants["ex_reflect_row_max"] = ex_of(_lib.PAD_REFLECT, None, True)
+    ex_baseline = base is not None and hasattr(base, "zflac_hip_mel_run_ex")
+    if ex_baseline:  # k_mel_ex and k_mel_norm of the baseline build, each beside its own leg
+        variants["ex_reflect_baseline"] = ex_of(_lib.PAD_REFLECT, None, False, base, base_plan)
+        variants["ex_reflect_lengths_baseline"] = ex_of(_lib.PAD_REFLECT, lengths, False, base, base_plan)
+        variants["ex_reflect_row_max_baseline"] = ex_of(_lib.PAD_REFLECT, None, True, base, base_plan)
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -171,6 +181,10 @@ def main():
     if base is not None:
         b, n = res["run_baseline"], res["run"]
         res["run_median_within_baseline_spread"] = b["min_ms"] <= n["median_ms"] <= b["max_ms"] or n["median_ms"] < b["min_ms"]
+    if ex_baseline:
+        for name in ("ex_reflect", "ex_reflect_lengths", "ex_reflect_row_max"):
+            b, n = res[name + "_baseline"], res[name]
+            res[name + "_median_within_baseline_range"] = b["min_ms"] <= n["median_ms"] <= b["max_ms"]
     L.zflac_hip_mel_destroy(plan)
     if base is not None:
         base.zflac_hip_mel_destroy(base_plan)

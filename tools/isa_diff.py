@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/isa_diff.py <parent.s> <branch.s> [--json out.json]: do two gfx950 device listings hold
+"""tools/isa_diff.py <parent.s> <branch.s> [--json out.json [--brief]]: do two gfx950 device listings hold
 the same kernels? (hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -x hip -I include
 --cuda-device-only -S unit.hip). With two directories: every <name>.s found in both.
 
@@ -91,6 +91,13 @@ def main():
     else:
         res = {os.path.basename(pb)[:-2]: diff(pa, pb)}
     txt = json.dumps(res, indent=1)
+    if "--brief" in sys.argv:  # a file to commit: no opcode histograms, one line per differing kernel
+        units = []
+        for unit, r in res.items():
+            head = json.dumps({k: v for k, v in r.items() if k != "differences"})[:-1]
+            diffs = ",\n".join("   " + json.dumps({k: v for k, v in d.items() if k != "ops"}) for d in r["differences"])
+            units.append(f' {json.dumps(unit)}: {head}, "differences": [' + ("\n" + diffs + "\n  " if diffs else "") + "]}")
+        txt = "{\n" + ",\n".join(units) + "\n}"
     if out:
         open(out, "w").write(txt + "\n")
     for unit, r in res.items():

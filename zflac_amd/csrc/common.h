@@ -390,6 +390,10 @@ constexpr uint32_t MEL_SLAB = 64;                            // samples of every
 constexpr uint32_t MEL_PAIR_STRIDE = 2 * MEL_FRAMES + 16;    // floats of LDS per sample pair of the staged frames
 constexpr uint32_t MEL_LDS_FLOATS = MEL_SLAB * 2 * MEL_TILE + (MEL_SLAB / 2) * MEL_PAIR_STRIDE;
 
+// Row of a 32 x 32 MFMA accumulator that register r holds in lanes 0..31 (lanes 32..63: + 4).
+// The kernels' epilogue (mel_tile.h) and the filter table's layout (mel_plan.cpp) both go by it.
+constexpr uint32_t mel_acc_row(uint32_t r) { return (r & 3) + 8 * (r >> 2); }
+
 struct MelArgs {
     const float* wave;     // rows of row_stride floats
     const float* basis;    // mel_plan.h: [bin tile][sample pair][re, im][sample of the pair][bin]
@@ -400,7 +404,7 @@ struct MelArgs {
     uint64_t first_frame;  // feature frame of destination frame 0
     uint64_t frames;       // destination frames per row
     uint32_t tiles;        // workgroups per row: ceil(frames / MEL_FRAMES); grid = rows * tiles
-    uint32_t n_fft, hop;   // the frame span the sums run over (N; a framed plan: Nw, padded as its table), hop
+    uint32_t span, hop;    // samples of a frame the sums run over (N; a framed plan: Nw, padded as its table), hop
     int32_t off;           // frame t starts at sample t * hop - off (center ? N / 2 : 0; a framed plan: mel_plan.h)
     uint32_t n_bins;       // rows of the filterbank
     uint32_t bin_tiles;    // ceil((N / 2 + 1) / MEL_TILE), N the DFT size

@@ -39,6 +39,7 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "dispatch.h"
 #include "export_tile.h"
 #include "launch.h"
 #include "mix_tile.h"
@@ -69,48 +70,32 @@ __global__ __launch_bounds__(EXPORT_THREADS) void k_export_mixed(ExportArgs a, c
     else export_tile<DT, LAYOUT>(row, r, a.channels, a.frames, a.vec, (uint64_t)tile * EXPORT_TILE);
 }
 
-template <int DT>
-hipError_t launch_mixed_dt(int layout, const ExportArgs& a, const float* coef, uint32_t blocks, hipStream_t st) {
-    if (layout == ZFLAC_LAYOUT_PLANAR)
-        hipLaunchKernelGGL((k_export_mixed<DT, ZFLAC_LAYOUT_PLANAR>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a, coef);
-    else
-        hipLaunchKernelGGL((k_export_mixed<DT, ZFLAC_LAYOUT_INTERLEAVED>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a, coef);
-    return hipGetLastError();
-}
-
-template <int DT>
-hipError_t launch_dt(int layout, const ExportArgs& a, uint32_t blocks, hipStream_t st) {
-    if (layout == ZFLAC_LAYOUT_PLANAR)
-        hipLaunchKernelGGL((k_export<DT, ZFLAC_LAYOUT_PLANAR>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_export<DT, ZFLAC_LAYOUT_INTERLEAVED>), dim3(blocks), dim3(EXPORT_THREADS), 0, st, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 // a.n_rows * a.tiles workgroups (the caller keeps the product within gridDim.x's 2^31 - 1)
 hipError_t launch_export(int dtype, int layout, const ExportArgs& a, hipStream_t st) {
     const uint32_t blocks = a.n_rows * a.tiles;
     if (blocks == 0) return hipSuccess;
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32>(layout, a, blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16>(layout, a, blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16>(layout, a, blocks, st);
-        default: return launch_dt<ZFLAC_EXPORT_I32>(layout, a, blocks, st);
-    }
+    return dispatch_else<ZFLAC_EXPORT_F32, ZFLAC_EXPORT_F16, ZFLAC_EXPORT_BF16, ZFLAC_EXPORT_I32>(dtype, [&](auto dt) {
+        return dispatch_else<ZFLAC_LAYOUT_PLANAR, ZFLAC_LAYOUT_INTERLEAVED>(layout, [&](auto lay) {
+            hipLaunchKernelGGL((k_export<decltype(dt)::value, decltype(lay)::value>), dim3(blocks), dim3(EXPORT_THREADS), 0,
+                               st, a);
+            return hipGetLastError();
+        });
+    });
 }
 
 // the same grid; dtype is F32, F16 or BF16, a.channels at most MIX_MAX_CH, coef the call's table
 hipError_t launch_export_mixed(int dtype, int layout, const ExportArgs& a, const float* coef, hipStream_t st) {
     const uint32_t blocks = a.n_rows * a.tiles;
     if (blocks == 0) return hipSuccess;
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_mixed_dt<ZFLAC_EXPORT_F32>(layout, a, coef, blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_mixed_dt<ZFLAC_EXPORT_F16>(layout, a, coef, blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_mixed_dt<ZFLAC_EXPORT_BF16>(layout, a, coef, blocks, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_float(dtype, [&](auto dt) {
+        return dispatch_else<ZFLAC_LAYOUT_PLANAR, ZFLAC_LAYOUT_INTERLEAVED>(layout, [&](auto lay) {
+            hipLaunchKernelGGL((k_export_mixed<decltype(dt)::value, decltype(lay)::value>), dim3(blocks),
+                               dim3(EXPORT_THREADS), 0, st, a, coef);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace zflac

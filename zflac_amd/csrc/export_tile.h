@@ -57,6 +57,15 @@ __device__ __forceinline__ typename Out<DT>::T conv_f32(float f) {
     }
 }
 
+// Its inverse, exact: an element of the output dtype as f32
+template <int DT>
+__device__ __forceinline__ float widen_f32(typename Out<DT>::T e) {
+    static_assert(DT != ZFLAC_EXPORT_I32, "a float dtype");
+    if constexpr (DT == ZFLAC_EXPORT_F32) return e;
+    else if constexpr (DT == ZFLAC_EXPORT_F16) return (float)e;
+    else return __uint_as_float((uint32_t)e << 16);
+}
+
 // int -> float rounds to nearest-even (25..32-bit samples), the scale is exact
 template <int DT>
 __device__ __forceinline__ typename Out<DT>::T conv(int32_t v, float scale) {

@@ -38,30 +38,33 @@
 // that reads x[rho(s)]. The epilogue takes the maximum of the f32 values a lane stores, a wave
 // reduces it and one atomic per wave goes to row_max[row] (-inf before the launch). k_mel_norm is
 // the elementwise pass behind it (ZFLAC_NORM_ROW_MAX).
+//
+// The frame origin, the row length, rho, the second product and the epilogue are mel_tile.h's,
+// which k_mel_split (mel_bf16.hip) shares; this unit owns the staging through LDS and the f32
+// MFMA loop.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "dispatch.h"
 #include "export_tile.h"
 #include "launch.h"
+#include "mel_tile.h"
 
 namespace zflac {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// One workgroup's tile. EX = false is zflac_hip_mel_run's kernel as it always was; EX = true
-// (zflac_hip_mel_run_ex) adds the row's own length, reflect padding and the row maximum. FR (with
-// EX): a framed plan, whose reflect bound is half the DFT size rather than half the span and which
-// may ask for ZFLAC_PAD_MIRROR; FR = false is k_mel_ex as it was before framed plans, statement for
-// statement, so the plans that existed run the code they had.
+// One workgroup's tile. EX = false is zflac_hip_mel_run's kernel; EX = true (zflac_hip_mel_run_ex)
+// adds the row's own length, reflect padding and the row maximum. FR (with EX): a framed plan,
+// with mel_tile.h's signed origin and its padding rule for such plans. FR is a template flag, not
+// a run-time one, so that the plans without a frame of their own run the code they always had.
 template <int DT, int LAYOUT, int MT, bool EX, bool FR>
 __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengths, float* row_max, uint32_t pad,
                                          uint32_t pad_half) {
-    using OT = typename Out<DT>::T;
     __shared__ __attribute__((aligned(16))) float lds[MEL_LDS_FLOATS];
     float* const lb = lds;                               // basis slab
     float* const lf = lds + MEL_SLAB * 2 * MEL_TILE;     // frames slab
@@ -69,21 +72,15 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
     const uint64_t row = blockIdx.x / a.tiles;
     const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
     const float* const x = a.wave + row * a.row_stride;
-    const uint32_t N = a.n_fft;  // the frame span: the DFT size, or a framed plan's (padded) frame length
+    const uint32_t N = a.span;
     // the row's length, and whether this tile needs the reflection: both uniform, decided once.
-    // An interior tile (every sample index of its 128 frames inside [0, n_row)) stages as ever.
+    // An interior tile stages as ever.
     uint64_t n_row = a.wave_frames;
     bool edge = false;
-    const int64_t off = EX && !FR ? (int64_t)(uint32_t)a.off : (int64_t)a.off;  // (negative for some framed plans)
+    const int64_t off = mel_origin<!EX || FR>(a);
     if constexpr (EX) {
-        if (lengths) {
-            const uint64_t n = lengths[row];
-            n_row = n < a.wave_frames ? n : a.wave_frames;
-        }
-        if (FR ? pad != ZFLAC_PAD_ZEROS : pad == ZFLAC_PAD_REFLECT) {
-            const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - off;
-            edge = lo < 0 || (uint64_t)lo + (uint64_t)(MEL_FRAMES - 1) * a.hop + N > n_row;
-        }
+        n_row = mel_row_length(a, lengths, row);
+        if (mel_pads<FR>(pad)) edge = !mel_tile_inside(a, j0, off, n_row);
     }
 
     // staging of the frames: this thread's sample of every eight and its frame of every 32
@@ -114,19 +111,12 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
             const float* const bs = bb + (size_t)n0 * (2 * MEL_TILE);
             for (uint32_t i = tid * 4; i < ns * (2 * MEL_TILE); i += MEL_THREADS * 4)
                 *reinterpret_cast<f32x4*>(lb + i) = *reinterpret_cast<const f32x4*>(bs + i);
-            if (EX && edge) {  // x~[s] = x[rho(s)]: one reflection about 0 or n_row - 1, zero beyond it
-                // _REFLECT: rho(s) = -s, 2 (n_row - 1) - s, inside the signal padded by half the DFT size;
-                // _MIRROR repeats the edge sample (m = 1): rho(s) = -1 - s, 2 n_row - 1 - s, no other bound
-                const int64_t nr = (int64_t)n_row, m = FR && pad == ZFLAC_PAD_MIRROR;
-                const int64_t half = !FR ? (int64_t)(N / 2) : m ? (int64_t)1 << 62 : (int64_t)pad_half;
+            if (EX && edge) {
+                const MelPad<FR> padded(a, n_row, pad, pad_half);
                 for (uint32_t n = st_n; n < ns; n += 8) {
                     float v[MEL_WAVES];
 #pragma unroll
-                    for (uint32_t g = 0; g < MEL_WAVES; g++) {
-                        const int64_t s = st_base[g] + (int64_t)(n0 + n);
-                        const int64_t r = s < 0 ? -s - m : (s >= nr ? 2 * (nr - 1) + m - s : s);
-                        v[g] = st_ok[g] && s >= -half && s < nr + half && r >= 0 && r < nr ? x[r] : 0.0f;
-                    }
+                    for (uint32_t g = 0; g < MEL_WAVES; g++) v[g] = padded.read(x, st_base[g] + (int64_t)(n0 + n), st_ok[g]);
 #pragma unroll
                     for (uint32_t g = 0; g < MEL_WAVES; g++)
                         lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
@@ -135,10 +125,8 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
                 for (uint32_t n = st_n; n < ns; n += 8) {
                     float v[MEL_WAVES];
 #pragma unroll
-                    for (uint32_t g = 0; g < MEL_WAVES; g++) {
-                        const int64_t s = st_base[g] + (int64_t)(n0 + n);
-                        v[g] = st_ok[g] && s >= 0 && (uint64_t)s < n_row ? x[s] : 0.0f;
-                    }
+                    for (uint32_t g = 0; g < MEL_WAVES; g++)
+                        v[g] = mel_read_zeros(x, st_base[g] + (int64_t)(n0 + n), n_row, st_ok[g]);
 #pragma unroll
                     for (uint32_t g = 0; g < MEL_WAVES; g++)
                         lf[(n >> 1) * MEL_PAIR_STRIDE + 2 * (st_j + MEL_TILE * g) + (n & 1)] = v[g];
@@ -159,50 +147,14 @@ __device__ __forceinline__ void mel_tile(const MelArgs& a, const uint64_t* lengt
                 for (uint32_t s = 0; s < ns / 2; s++) pair(s);
             }
         }
-        const float* const fb = a.filters + (size_t)b * (16 * MT * 64) + lane;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const float p = __builtin_fmaf(im[r], im[r], re[r] * re[r]);
-#pragma unroll
-            for (int q = 0; q < MT; q++) V[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[(r * MT + q) * 64], p, V[q], 0, 0, 0);
-        }
+        mel_filter<MT>(V, a.filters + (size_t)b * (16 * MT * 64) + lane, re, im);
     }
 
     const uint64_t j = j0 + wv * MEL_TILE + (lane & 31);
     if constexpr (!EX) {
         if (j >= a.frames) return;
     }
-    OT* const dst = static_cast<OT*>(a.dst);
-    float mx = -__builtin_inff();  // of the f32 values this lane stores
-    if (j < a.frames) {
-#pragma unroll
-        for (int q = 0; q < MT; q++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const uint32_t m = q * MEL_TILE + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= a.n_bins) continue;
-                float v = V[q][r];
-                if (a.scale == ZFLAC_MEL_LOG10) v = log10f(fmaxf(v, a.floor));
-                else if (a.scale == ZFLAC_MEL_LN) v = logf(fmaxf(v, a.floor));
-                const uint64_t at = LAYOUT == ZFLAC_MEL_BINS_FIRST ? (row * a.n_bins + m) * a.frames + j
-                                                                   : (row * a.frames + j) * a.n_bins + m;
-                dst[at] = conv_f32<DT>(v);
-                if constexpr (EX) mx = fmaxf(mx, v);
-            }
-    }
-    if constexpr (EX) {
-        // the row maximum: the wave's, then one atomic on the float's bits (signed max for the
-        // non-negative, unsigned min for the negative: the larger negative float has the smaller bits)
-        if (row_max) {
-#pragma unroll
-            for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-            const uint32_t u = __float_as_uint(mx);
-            if (lane == 0 && u != 0xFF800000u) {
-                if (u >> 31) atomicMin(reinterpret_cast<unsigned int*>(row_max + row), u);
-                else atomicMax(reinterpret_cast<int*>(row_max + row), (int)u);
-            }
-        }
-    }
+    mel_store<DT, LAYOUT, MT, EX>(a, V, row, j, lane, row_max);
 }
 
 template <int DT, int LAYOUT, int MT>
@@ -222,11 +174,7 @@ __global__ __launch_bounds__(MEL_THREADS) void k_mel_ex(MelExArgs e) {
 template <int DT>
 __device__ __forceinline__ typename Out<DT>::T mel_norm1(typename Out<DT>::T e, float thr, float add, float mul) {
 #pragma clang fp contract(off)
-    float l;
-    if constexpr (DT == ZFLAC_EXPORT_F32) l = e;
-    else if constexpr (DT == ZFLAC_EXPORT_F16) l = (float)e;
-    else l = __uint_as_float((uint32_t)e << 16);
-    const float c = fmaxf(l, thr);
+    const float c = fmaxf(widen_f32<DT>(e), thr);
     const float s = c + add;
     return conv_f32<DT>(s * mul);
 }
@@ -268,40 +216,22 @@ __global__ __launch_bounds__(MEL_NORM_THREADS) void k_mel_norm(MelNormArgs a) {
     }
 }
 
-// EX: 0 k_mel, 1 k_mel_ex as it was, 2 k_mel_ex of a framed plan
-template <int DT, int LAYOUT, int EX, typename A>
-hipError_t launch_mt(uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
-#define ZFLAC_MEL_LAUNCH(MT)                                                                                          \
-    if constexpr (EX) hipLaunchKernelGGL((k_mel_ex<DT, LAYOUT, MT, EX == 2>), dim3(blocks), dim3(MEL_THREADS), 0, st, a); \
-    else hipLaunchKernelGGL((k_mel<DT, LAYOUT, MT>), dim3(blocks), dim3(MEL_THREADS), 0, st, a);                         \
-    break
-    switch (m_tiles) {
-        case 1: ZFLAC_MEL_LAUNCH(1);
-        case 2: ZFLAC_MEL_LAUNCH(2);
-        case 4: ZFLAC_MEL_LAUNCH(4);
-        case 8: ZFLAC_MEL_LAUNCH(8);
-        default: return hipErrorInvalidValue;
-    }
-#undef ZFLAC_MEL_LAUNCH
-    return hipGetLastError();
-}
-
-template <int DT, int EX, typename A>
-hipError_t launch_dt(int layout, uint32_t m_tiles, const A& a, uint32_t blocks, hipStream_t st) {
-    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, EX>(m_tiles, a, blocks, st)
-                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, EX>(m_tiles, a, blocks, st);
-}
-
+// EX: 0 k_mel, 1 k_mel_ex, 2 k_mel_ex of a framed plan
 template <int EX, typename A>
 hipError_t launch_any(int dtype, int layout, uint32_t m_tiles, const A& a, uint64_t blocks, hipStream_t st) {
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16, EX>(layout, m_tiles, a, (uint32_t)blocks, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_float(dtype, [&](auto dt) {
+        return dispatch_else<ZFLAC_MEL_BINS_FIRST, ZFLAC_MEL_FRAMES_FIRST>(layout, [&](auto lay) {
+            return dispatch<1, 2, 4, 8>(m_tiles, [&](auto mt) {
+                constexpr int DT = decltype(dt)::value, LAYOUT = decltype(lay)::value, MT = decltype(mt)::value;
+                const dim3 grid((uint32_t)blocks), block(MEL_THREADS);
+                if constexpr (EX) hipLaunchKernelGGL((k_mel_ex<DT, LAYOUT, MT, EX == 2>), grid, block, 0, st, a);
+                else hipLaunchKernelGGL((k_mel<DT, LAYOUT, MT>), grid, block, 0, st, a);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -321,13 +251,10 @@ hipError_t launch_mel_ex(int dtype, int layout, uint32_t m_tiles, bool framed, c
 hipError_t launch_mel_norm(int dtype, const MelNormArgs& a, hipStream_t st) {
     if (a.total == 0) return hipSuccess;
     const uint32_t blocks = a.total < 0x7FFFFFFFull ? (uint32_t)a.total : 0x7FFFFFFFu;
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_F32>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
-        case ZFLAC_EXPORT_F16: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_F16>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
-        case ZFLAC_EXPORT_BF16: hipLaunchKernelGGL((k_mel_norm<ZFLAC_EXPORT_BF16>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_float(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((k_mel_norm<decltype(dt)::value>), dim3(blocks), dim3(MEL_NORM_THREADS), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace zflac

@@ -7,10 +7,12 @@
 // i + j <= 2 (TERMS = 6) or <= 1 (TERMS = 3) are kept: the rest lies 3 * 2^-24 (2^-14) below
 // |c| |x|. So
 //   X[2 K x frames] = sum over (i, j) kept of  basis_i^T [2 K x N] . frames_j [N x frames]
-// with f32 accumulation inside the matrix cores, and everything behind it is k_mel's: P = re^2 +
-// im^2 element by element in the accumulators' registers, P's registers as the B operand of the
-// f32 MFMA against the filter table (the accumulator layout of the bf16 instruction is the f32
-// one's), the log, the conversion, the row maximum.
+// with f32 accumulation inside the matrix cores, and everything behind it is mel_tile.h's, the
+// code k_mel_ex runs: P = re^2 + im^2 element by element in the accumulators' registers, P's
+// registers as the B operand of the f32 MFMA against the filter table (the accumulator layout of
+// the bf16 instruction is the f32 one's), the log, the conversion, the row maximum. So are the
+// frame origin, the row length and the padding rule in front of it. This unit owns how the samples
+// and the pieces reach the bf16 MFMAs.
 //
 // The tile is k_mel's: a workgroup of MEL_WAVES waves takes MEL_FRAMES frames of one row, a wave
 // MEL_TILE of them, the frame on the lane (l & 31). The loop order is not: the samples go in
@@ -40,22 +42,21 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "dispatch.h"
 #include "export_tile.h"
 #include "launch.h"
+#include "mel_tile.h"
 
 namespace zflac {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-// FR: a framed plan (a frame shorter than the DFT or a Kaldi framing). FR = false is the kernel as
-// it was before framed plans, statement for statement: the start offset is the unsigned N / 2 or 0,
-// the reflect bound is half the span and there is no mirror, so the plans that existed compile to
-// the code they had (a shared body cost k_mel_split 1 % on Whisper's shape).
+// FR: a framed plan (a frame shorter than the DFT or a Kaldi framing), with mel_tile.h's signed
+// origin and its padding rule for such plans. A template flag, not a run-time one: a shared body
+// cost the plans without a frame of their own 1 % on Whisper's shape.
 template <int DT, int LAYOUT, int MT, int TERMS, bool FR>
 __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelSplitArgs sa) {
-    using OT = typename Out<DT>::T;
     constexpr uint32_t NP = TERMS == 6 ? 3 : 2;                  // pieces of an operand in use
     constexpr uint32_t OPS = 2 * NP * 64;                        // 16-byte vectors of a bin tile's A operands
     constexpr uint32_t SLAB = MEL_BF16_GROUP * OPS;              // ... of a group, per sample block
@@ -66,14 +67,10 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
     const uint64_t row = blockIdx.x / a.tiles;
     const uint64_t j0 = (uint64_t)(blockIdx.x - row * a.tiles) * MEL_FRAMES;  // first destination frame
     const float* const x = a.wave + row * a.row_stride;
-    const uint32_t N = a.n_fft;  // the frame span: the DFT size, or a framed plan's frame length
-    uint64_t n_row = a.wave_frames;
-    if (sa.e.lengths) {
-        const uint64_t n = sa.e.lengths[row];
-        n_row = n < a.wave_frames ? n : a.wave_frames;
-    }
-    const bool reflect = FR ? sa.e.pad != ZFLAC_PAD_ZEROS : sa.e.pad == ZFLAC_PAD_REFLECT;  // FR: or _MIRROR
-    const int64_t off = FR ? (int64_t)a.off : (int64_t)(uint32_t)a.off;
+    const uint32_t N = a.span;
+    const uint64_t n_row = mel_row_length(a, sa.e.lengths, row);
+    const bool reflect = mel_pads<FR>(sa.e.pad);
+    const int64_t off = mel_origin<FR>(a);
     // this lane's frame, and sample 8 (l >> 5) of it: where its eight samples of block 0 start
     const uint64_t j = j0 + wv * MEL_TILE + (lane & 31);
     const bool ok = j < a.frames;
@@ -81,33 +78,20 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
     const int64_t base = ok ? (int64_t)((a.first_frame + j) * a.hop) - off + n_lane : 0;
     // interior (uniform): every frame of the tile exists and every sample index the workgroup
     // forms lies in [0, n_row), blocks of padding (n >= N) included: nothing to decide per sample
-    const int64_t lo = (int64_t)((a.first_frame + j0) * a.hop) - off;
-    const bool interior = N % MEL_BF16_K == 0 && j0 + MEL_FRAMES <= a.frames && lo >= 0 &&
-                          (uint64_t)lo + (uint64_t)(MEL_FRAMES - 1) * a.hop + N <= n_row;
+    const bool interior = N % MEL_BF16_K == 0 && j0 + MEL_FRAMES <= a.frames && mel_tile_inside(a, j0, off, n_row);
 
     auto fetch = [&](uint32_t kb, float (&v)[8]) {
         const int64_t s0 = base + (int64_t)(kb * MEL_BF16_K);
         if (interior) {
 #pragma unroll
             for (int i = 0; i < 8; i++) v[i] = x[s0 + i];
-        } else if (reflect) {  // x~[s] = x[rho(s)]: one reflection about 0 or n_row - 1, zero beyond it
-            // (k_mel_ex's rule: _MIRROR repeats the edge sample, m = 1, and has no bound but the row)
-            const int64_t nr = (int64_t)n_row, m = FR && sa.e.pad == ZFLAC_PAD_MIRROR;
-            const int64_t half = !FR ? (int64_t)(N / 2) : m ? (int64_t)1 << 62 : (int64_t)sa.e.pad_half;
+        } else if (reflect) {
+            const MelPad<FR> padded(a, n_row, sa.e.pad, sa.e.pad_half);
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int64_t s = s0 + i;
-                const int64_t r = s < 0 ? -s - m : (s >= nr ? 2 * (nr - 1) + m - s : s);
-                const bool in = ok && kb * MEL_BF16_K + n_lane + i < N && s >= -half && s < nr + half && r >= 0 && r < nr;
-                v[i] = in ? x[r] : 0.0f;
-            }
+            for (int i = 0; i < 8; i++) v[i] = padded.read(x, s0 + i, ok && kb * MEL_BF16_K + n_lane + i < N);
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int64_t s = s0 + i;
-                const bool in = ok && kb * MEL_BF16_K + n_lane + i < N && s >= 0 && (uint64_t)s < n_row;
-                v[i] = in ? x[s] : 0.0f;
-            }
+            for (int i = 0; i < 8; i++) v[i] = mel_read_zeros(x, s0 + i, n_row, ok && kb * MEL_BF16_K + n_lane + i < N);
         }
     };
 
@@ -196,81 +180,11 @@ __global__ __launch_bounds__(MEL_THREADS, MT <= 4 ? 2 : 1) void k_mel_split(MelS
 #pragma unroll
         for (uint32_t g = 0; g < MEL_BF16_GROUP; g++) {
             if (g < tg) {
-                const float* const fb = a.filters + (size_t)(b0 + g) * (16 * MT * 64) + lane;
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const float p = __builtin_fmaf(im[g][r], im[g][r], re[g][r] * re[g][r]);
-#pragma unroll
-                    for (int q = 0; q < MT; q++)
-                        V[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[(r * MT + q) * 64], p, V[q], 0, 0, 0);
-                }
+                mel_filter<MT>(V, a.filters + (size_t)(b0 + g) * (16 * MT * 64) + lane, re[g], im[g]);
             }
         }
     }
-
-    // k_mel_ex's epilogue
-    OT* const dst = static_cast<OT*>(a.dst);
-    float mx = -__builtin_inff();  // of the f32 values this lane stores
-    if (ok) {
-#pragma unroll
-        for (int q = 0; q < MT; q++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const uint32_t m = q * MEL_TILE + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= a.n_bins) continue;
-                float v = V[q][r];
-                if (a.scale == ZFLAC_MEL_LOG10) v = log10f(fmaxf(v, a.floor));
-                else if (a.scale == ZFLAC_MEL_LN) v = logf(fmaxf(v, a.floor));
-                const uint64_t at = LAYOUT == ZFLAC_MEL_BINS_FIRST ? (row * a.n_bins + m) * a.frames + j
-                                                                   : (row * a.frames + j) * a.n_bins + m;
-                dst[at] = conv_f32<DT>(v);
-                mx = fmaxf(mx, v);
-            }
-    }
-    // the row maximum: the wave's, then one atomic on the float's bits (signed max for the
-    // non-negative, unsigned min for the negative: the larger negative float has the smaller bits)
-    float* const row_max = sa.e.row_max;
-    if (row_max) {
-#pragma unroll
-        for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        const uint32_t u = __float_as_uint(mx);
-        if (lane == 0 && u != 0xFF800000u) {
-            if (u >> 31) atomicMin(reinterpret_cast<unsigned int*>(row_max + row), u);
-            else atomicMax(reinterpret_cast<int*>(row_max + row), (int)u);
-        }
-    }
-}
-
-template <int DT, int LAYOUT, int TERMS, bool FR>
-hipError_t launch_mt(uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
-#define ZFLAC_MEL_LAUNCH(MT) \
-    hipLaunchKernelGGL((k_mel_split<DT, LAYOUT, MT, TERMS, FR>), dim3(blocks), dim3(MEL_THREADS), 0, st, s); \
-    break
-    switch (m_tiles) {
-        case 1: ZFLAC_MEL_LAUNCH(1);
-        case 2: ZFLAC_MEL_LAUNCH(2);
-        case 4: ZFLAC_MEL_LAUNCH(4);
-        case 8: ZFLAC_MEL_LAUNCH(8);
-        default: return hipErrorInvalidValue;
-    }
-#undef ZFLAC_MEL_LAUNCH
-    return hipGetLastError();
-}
-
-template <int DT, int TERMS, bool FR>
-hipError_t launch_layout(int layout, uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
-    return layout == ZFLAC_MEL_BINS_FIRST ? launch_mt<DT, ZFLAC_MEL_BINS_FIRST, TERMS, FR>(m_tiles, s, blocks, st)
-                                          : launch_mt<DT, ZFLAC_MEL_FRAMES_FIRST, TERMS, FR>(m_tiles, s, blocks, st);
-}
-
-template <int TERMS, bool FR>
-hipError_t launch_dt(int dtype, int layout, uint32_t m_tiles, const MelSplitArgs& s, uint32_t blocks, hipStream_t st) {
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_layout<ZFLAC_EXPORT_F32, TERMS, FR>(layout, m_tiles, s, blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_layout<ZFLAC_EXPORT_F16, TERMS, FR>(layout, m_tiles, s, blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_layout<ZFLAC_EXPORT_BF16, TERMS, FR>(layout, m_tiles, s, blocks, st);
-        default: return hipErrorInvalidValue;
-    }
+    mel_store<DT, LAYOUT, MT, true>(a, V, row, j, lane, sa.e.row_max);
 }
 
 }  // namespace
@@ -281,11 +195,20 @@ hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t te
     const uint64_t blocks = rows * s.e.a.tiles;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull || !s.pieces) return hipErrorInvalidValue;
-    if (terms == 6) return framed ? launch_dt<6, true>(dtype, layout, m_tiles, s, (uint32_t)blocks, st)
-                                  : launch_dt<6, false>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
-    if (terms == 3) return framed ? launch_dt<3, true>(dtype, layout, m_tiles, s, (uint32_t)blocks, st)
-                                  : launch_dt<3, false>(dtype, layout, m_tiles, s, (uint32_t)blocks, st);
-    return hipErrorInvalidValue;
+    return dispatch<6, 3>(terms, [&](auto tm) {
+        return dispatch<true, false>(framed, [&](auto fr) {
+            return dispatch_float(dtype, [&](auto dt) {
+                return dispatch_else<ZFLAC_MEL_BINS_FIRST, ZFLAC_MEL_FRAMES_FIRST>(layout, [&](auto lay) {
+                    return dispatch<1, 2, 4, 8>(m_tiles, [&](auto mt) {
+                        hipLaunchKernelGGL((k_mel_split<decltype(dt)::value, decltype(lay)::value, decltype(mt)::value,
+                                                        decltype(tm)::value, decltype(fr)::value>),
+                                           dim3((uint32_t)blocks), dim3(MEL_THREADS), 0, st, s);
+                        return hipGetLastError();
+                    });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace zflac

@@ -24,24 +24,18 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "dispatch.h"
 #include "export_tile.h"
 #include "launch.h"
 
 namespace zflac {
 namespace {
 
-template <int DT>
-__device__ __forceinline__ float cmvn_widen(typename Out<DT>::T e) {
-    if constexpr (DT == ZFLAC_EXPORT_F32) return e;
-    else if constexpr (DT == ZFLAC_EXPORT_F16) return (float)e;
-    else return __uint_as_float((uint32_t)e << 16);
-}
-
 // conv((l - mu32) * r): two f32 roundings, nothing fused
 template <int DT>
 __device__ __forceinline__ typename Out<DT>::T cmvn_norm1(typename Out<DT>::T e, float mu32, float r) {
 #pragma clang fp contract(off)
-    const float d = cmvn_widen<DT>(e) - mu32;
+    const float d = widen_f32<DT>(e) - mu32;
     return conv_f32<DT>(d * r);
 }
 
@@ -101,10 +95,10 @@ __global__ __launch_bounds__(MEL_CMVN_THREADS) void k_mel_cmvn_bins(MelCmvnArgs 
                 OT e[VEC];
                 __builtin_memcpy(e, &q, 16);
 #pragma unroll
-                for (uint32_t k = 0; k < VEC; k++) l[k] = cmvn_widen<DT>(e[k]);
+                for (uint32_t k = 0; k < VEC; k++) l[k] = widen_f32<DT>(e[k]);
             } else {
 #pragma unroll
-                for (uint32_t k = 0; k < VEC; k++) l[k] = j + k < end ? cmvn_widen<DT>(p[j + k]) : 0.0f;
+                for (uint32_t k = 0; k < VEC; k++) l[k] = j + k < end ? widen_f32<DT>(p[j + k]) : 0.0f;
             }
         };
         const uint64_t chunks = (F + VEC - 1) / VEC;
@@ -188,13 +182,13 @@ __global__ __launch_bounds__(MEL_CMVN_THREADS) void k_mel_cmvn_frames(MelCmvnArg
         };
         double s = 0.0;
         if (on)
-            for (uint64_t j = g; j < F; j += G) s += (double)cmvn_widen<DT>(p[j * nb]);
+            for (uint64_t j = g; j < F; j += G) s += (double)widen_f32<DT>(p[j * nb]);
         const double mu = F ? bin_sum(s) / (double)F : 0.0;
         double ss = 0.0;
         if (a.mode == ZFLAC_CMVN_MEAN_VAR && F) {  // (uniform)
             if (on)
                 for (uint64_t j = g; j < F; j += G) {
-                    const double d = (double)cmvn_widen<DT>(p[j * nb]) - mu;
+                    const double d = (double)widen_f32<DT>(p[j * nb]) - mu;
                     ss += d * d;
                 }
             ss = bin_sum(ss);
@@ -210,13 +204,6 @@ __global__ __launch_bounds__(MEL_CMVN_THREADS) void k_mel_cmvn_frames(MelCmvnArg
     }
 }
 
-template <int DT>
-hipError_t launch_layout(int layout, const MelCmvnArgs& a, uint32_t blocks, hipStream_t st) {
-    if (layout == ZFLAC_MEL_BINS_FIRST) hipLaunchKernelGGL((k_mel_cmvn_bins<DT>), dim3(blocks), dim3(MEL_CMVN_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((k_mel_cmvn_frames<DT>), dim3(blocks), dim3(MEL_CMVN_THREADS), 0, st, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 // a.total passes over at most 2^31 - 1 workgroups
@@ -224,12 +211,13 @@ hipError_t launch_mel_cmvn(int dtype, int layout, const MelCmvnArgs& a, hipStrea
     if (a.total == 0) return hipSuccess;
     if (a.n_bins < 1 || a.n_bins > MEL_CMVN_THREADS) return hipErrorInvalidValue;
     const uint32_t blocks = a.total < 0x7FFFFFFFull ? (uint32_t)a.total : 0x7FFFFFFFu;
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_layout<ZFLAC_EXPORT_F32>(layout, a, blocks, st);
-        case ZFLAC_EXPORT_F16: return launch_layout<ZFLAC_EXPORT_F16>(layout, a, blocks, st);
-        case ZFLAC_EXPORT_BF16: return launch_layout<ZFLAC_EXPORT_BF16>(layout, a, blocks, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_float(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        const dim3 grid(blocks), block(MEL_CMVN_THREADS);
+        if (layout == ZFLAC_MEL_BINS_FIRST) hipLaunchKernelGGL((k_mel_cmvn_bins<DT>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_mel_cmvn_frames<DT>), grid, block, 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace zflac

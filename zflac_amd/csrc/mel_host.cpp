@@ -64,11 +64,14 @@ int mel_create_framed(const zflac_mel_desc* d, const zflac_mel_frame_desc* f, ui
 
 uint64_t mel_plan_frames_of(const zflac_mel* m, uint64_t n_samples) { return m ? mel_plan_frames(m->plan, n_samples) : 0; }
 
-// The launch arguments of a run the planner has accepted
-static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_frames, uint64_t row_stride,
-                        uint64_t first_frame, uint64_t frames, void* dst, const MelGrid& g) {
+// The launch arguments of a run the planner has accepted; what only zflac_hip_mel_run_ex can ask
+// for is off unless given
+static MelExArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_frames, uint64_t row_stride,
+                          uint64_t first_frame, uint64_t frames, void* dst, const MelGrid& g,
+                          const uint64_t* lengths = nullptr, float* row_max = nullptr, uint32_t pad = ZFLAC_PAD_ZEROS) {
     const MelPlan& p = m->plan;
-    MelArgs a;
+    MelExArgs e;
+    MelArgs& a = e.a;
     a.wave = wave;
     a.basis = m->basis.p;
     a.filters = m->filters.p;
@@ -78,16 +81,19 @@ static MelArgs mel_args(const zflac_mel* m, const float* wave, uint64_t wave_fra
     a.first_frame = first_frame;
     a.frames = frames;
     a.tiles = g.tiles;
-    // the span of the sums: the f32 table's sample rows; a split plan's frame length (its kernel
-    // reads zeros at and past it)
-    a.n_fft = p.math == ZFLAC_MEL_MATH_F32 ? p.span : p.win_length;
+    // the f32 table's sample rows; a split plan's frame length (its kernel reads zeros at and past it)
+    a.span = p.math == ZFLAC_MEL_MATH_F32 ? p.span : p.win_length;
     a.hop = p.hop;
     a.off = p.off;
     a.n_bins = p.n_bins;
     a.bin_tiles = p.bin_tiles;
     a.scale = p.scale;
     a.floor = p.floor;
-    return a;
+    e.lengths = lengths;
+    e.row_max = row_max;
+    e.pad = pad;
+    e.pad_half = p.n_fft / 2;
+    return e;
 }
 
 int mel_math(const zflac_mel* m) { return m ? (int)m->plan.math : -E_INVALID_ARGUMENT; }
@@ -102,21 +108,30 @@ static hipError_t launch_split(const zflac_mel* m, const MelExArgs& e, uint64_t 
     return launch_mel_split(p.dtype, p.layout, p.m_tiles, p.math == ZFLAC_MEL_MATH_BF16X6 ? 6 : 3, p.framed(), s, rows, st);
 }
 
+// launches(st) on the plan's device: on the caller's stream, or on the plan's own, and then the
+// call returns when the work is done
+template <typename F>
+static int mel_on_stream(zflac_mel* m, void* stream, F&& launches) {
+    return guarded([&]() -> int {
+        DeviceScope scope(m->device);
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
+        launches(st);
+        if (!stream) ck(hipStreamSynchronize(st));
+        return E_OK;
+    });
+}
+
 int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames, uint64_t row_stride,
             uint64_t first_frame, uint64_t frames, void* dst, size_t dst_bytes, void* stream) {
     MelGrid g;
     const int rc = mel_plan_run(m ? &m->plan : nullptr, reinterpret_cast<uintptr_t>(wave), rows, wave_frames, row_stride,
                                 first_frame, frames, reinterpret_cast<uintptr_t>(dst), dst_bytes, g);
     if (rc || g.blocks == 0) return rc;
-    return guarded([&]() -> int {
-        DeviceScope scope(m->device);
+    return mel_on_stream(m, stream, [&](hipStream_t st) {
         const MelPlan& p = m->plan;
-        const MelArgs a = mel_args(m, wave, wave_frames, row_stride, first_frame, frames, dst, g);
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
-        if (p.math == ZFLAC_MEL_MATH_F32) ck(launch_mel(p.dtype, p.layout, p.m_tiles, a, rows, st));
-        else ck(launch_split(m, MelExArgs{a, nullptr, nullptr, ZFLAC_PAD_ZEROS, p.n_fft / 2}, rows, st));
-        if (!stream) ck(hipStreamSynchronize(st));
-        return E_OK;
+        const MelExArgs e = mel_args(m, wave, wave_frames, row_stride, first_frame, frames, dst, g);
+        if (p.math == ZFLAC_MEL_MATH_F32) ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, rows, st));
+        else ck(launch_split(m, e, rows, st));
     });
 }
 
@@ -126,16 +141,10 @@ int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
     MelGrid g;
     const int rc = mel_plan_run_ex(m ? &m->plan : nullptr, r, g);
     if (rc || g.blocks == 0) return rc;
-    return guarded([&]() -> int {
-        DeviceScope scope(m->device);
+    return mel_on_stream(m, stream, [&](hipStream_t st) {
         const MelPlan& p = m->plan;
-        MelExArgs e;
-        e.a = mel_args(m, r->wave_device, r->wave_frames, r->row_stride, r->first_frame, r->frames, r->dst_device, g);
-        e.lengths = r->lengths_device;
-        e.row_max = r->row_max_device;
-        e.pad = r->pad;
-        e.pad_half = p.n_fft / 2;
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
+        const MelExArgs e = mel_args(m, r->wave_device, r->wave_frames, r->row_stride, r->first_frame, r->frames,
+                                     r->dst_device, g, r->lengths_device, r->row_max_device, r->pad);
         if (e.row_max) ck(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(e.row_max), (int)0xFF800000u, r->rows, st));
         if (p.math != ZFLAC_MEL_MATH_F32) ck(launch_split(m, e, r->rows, st));
         else if (mel_run_is_plain(*r)) ck(launch_mel(p.dtype, p.layout, p.m_tiles, e.a, r->rows, st));
@@ -152,8 +161,6 @@ int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream) {
             n.mul = r->mul;
             ck(launch_mel_norm(p.dtype, n, st));
         }
-        if (!stream) ck(hipStreamSynchronize(st));
-        return E_OK;
     });
 }
 
@@ -162,8 +169,7 @@ int mel_cmvn(zflac_mel* m, const zflac_mel_cmvn_desc* c, void* stream) {
     uint64_t passes = 0;
     const int rc = mel_plan_cmvn(m ? &m->plan : nullptr, c, passes);
     if (rc || passes == 0) return rc;
-    return guarded([&]() -> int {
-        DeviceScope scope(m->device);
+    return mel_on_stream(m, stream, [&](hipStream_t st) {
         const MelPlan& p = m->plan;
         MelCmvnArgs a;
         a.feat = c->feat_device;
@@ -178,10 +184,7 @@ int mel_cmvn(zflac_mel* m, const zflac_mel_cmvn_desc* c, void* stream) {
         a.ddof = c->ddof;
         a.eps = c->eps;
         a.pad_value = c->pad_value;
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : m->stream;
         ck(launch_mel_cmvn(p.dtype, p.layout, a, st));
-        if (!stream) ck(hipStreamSynchronize(st));
-        return E_OK;
     });
 }
 

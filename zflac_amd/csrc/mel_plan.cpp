@@ -123,7 +123,8 @@ size_t mel_basis_index(const MelPlan& p, uint32_t n, uint32_t k, uint32_t im) {
 size_t mel_filter_index(const MelPlan& p, uint32_t m, uint32_t k) {
     const size_t b = k / MEL_TILE, row = k % MEL_TILE, q = m / MEL_TILE;
     const size_t h = (row >> 2) & 1;                    // rows 4..7 of every eight sit in lanes 32..63
-    const size_t r = (row & 3) + 4 * (row >> 3);        // mel_acc_row(r) + 4 h == row
+    size_t r = 0;                                       // the register: mel_acc_row(r) + 4 h == row
+    while (mel_acc_row((uint32_t)r) + 4 * h != row) r++;
     return ((b * 16 + r) * p.m_tiles + q) * 64 + 32 * h + m % MEL_TILE;
 }
 

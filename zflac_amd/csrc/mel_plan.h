@@ -75,9 +75,6 @@ struct MelPlan {
     size_t elem_size() const { return dtype == ZFLAC_EXPORT_F32 ? 4 : 2; }
 };
 
-// Row of a 32 x 32 MFMA accumulator that register r holds in lanes 0..31 (lanes 32..63: + 4).
-constexpr uint32_t mel_acc_row(uint32_t r) { return (r & 3) + 8 * (r >> 2); }
-
 // zflac_hip_mel_create's checks, in this order: d and out (out_ptr: the caller's `out`, only
 // compared with NULL); size; dtype, layout, scale, center; n_fft; hop; n_bins; reserved; floor;
 // window and filters (NULL, then every value finite). E_OK fills p; nothing else is touched.

@@ -36,6 +36,7 @@
 
 #include "../../include/zflac_hip.h"
 #include "common.h"
+#include "dispatch.h"
 #include "export_tile.h"
 #include "launch.h"
 #include "mix_tile.h"
@@ -287,38 +288,25 @@ __global__ __launch_bounds__(RESAMPLE_THREADS) void k_resample_mixed(ResampleArg
     }
 }
 
-template <int DT, int LAYOUT>
-hipError_t launch_one(const ResampleArgs& a, const float* coef, uint32_t blocks, uint32_t lds_bytes, hipStream_t st) {
-    // above the 64 KiB a kernel may ask for by default
-    const void* k = coef ? reinterpret_cast<const void*>(&k_resample_mixed<DT, LAYOUT>)
-                         : reinterpret_cast<const void*>(&k_resample<DT, LAYOUT>);
-    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    if (coef)
-        hipLaunchKernelGGL((k_resample_mixed<DT, LAYOUT>), dim3(blocks), dim3(RESAMPLE_THREADS), lds_bytes, st, a, coef);
-    else
-        hipLaunchKernelGGL((k_resample<DT, LAYOUT>), dim3(blocks), dim3(RESAMPLE_THREADS), lds_bytes, st, a);
-    return hipGetLastError();
-}
-
-template <int DT>
-hipError_t launch_dt(int layout, const ResampleArgs& a, const float* coef, uint32_t blocks, uint32_t lds_bytes,
-                     hipStream_t st) {
-    if (layout == ZFLAC_LAYOUT_PLANAR) return launch_one<DT, ZFLAC_LAYOUT_PLANAR>(a, coef, blocks, lds_bytes, st);
-    return launch_one<DT, ZFLAC_LAYOUT_INTERLEAVED>(a, coef, blocks, lds_bytes, st);
-}
-
 // coef == nullptr: k_resample, else k_resample_mixed
 hipError_t launch_any(int dtype, int layout, const ResampleArgs& a, const float* coef, hipStream_t st) {
     const uint32_t blocks = a.n_rows * a.tiles;
     if (blocks == 0) return hipSuccess;
     const uint32_t lds_bytes = RESAMPLE_LDS_FLOATS * sizeof(float);
-    switch (dtype) {
-        case ZFLAC_EXPORT_F32: return launch_dt<ZFLAC_EXPORT_F32>(layout, a, coef, blocks, lds_bytes, st);
-        case ZFLAC_EXPORT_F16: return launch_dt<ZFLAC_EXPORT_F16>(layout, a, coef, blocks, lds_bytes, st);
-        case ZFLAC_EXPORT_BF16: return launch_dt<ZFLAC_EXPORT_BF16>(layout, a, coef, blocks, lds_bytes, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_float(dtype, [&](auto dt) {
+        return dispatch_else<ZFLAC_LAYOUT_PLANAR, ZFLAC_LAYOUT_INTERLEAVED>(layout, [&](auto lay) {
+            constexpr int DT = decltype(dt)::value, LAYOUT = decltype(lay)::value;
+            // above the 64 KiB a kernel may ask for by default
+            const void* k = coef ? reinterpret_cast<const void*>(&k_resample_mixed<DT, LAYOUT>)
+                                 : reinterpret_cast<const void*>(&k_resample<DT, LAYOUT>);
+            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (e != hipSuccess) return e;
+            const dim3 grid(blocks), block(RESAMPLE_THREADS);
+            if (coef) hipLaunchKernelGGL((k_resample_mixed<DT, LAYOUT>), grid, block, lds_bytes, st, a, coef);
+            else hipLaunchKernelGGL((k_resample<DT, LAYOUT>), grid, block, lds_bytes, st, a);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace
