@@ -182,11 +182,21 @@ def _crc_rows(buf: np.ndarray, starts, ends, table, width: int) -> np.ndarray:
     crc = np.zeros(s.size, np.uint32)
     mask, sh = np.uint32((1 << width) - 1), np.uint32(width - 8)
     live = s.size
-    for j in range(int(length[0]) if s.size else 0):
-        while length[live - 1] <= j:
+    j = 0
+    while live and j < int(length[0]):
+        while live and length[live - 1] <= j:
             live -= 1
+        if live <= 2:  # a few rows far longer than the rest (a 2 MiB frame): plain integers from here
+            tab, m, k = table.tolist(), int(mask), int(sh)
+            for i in range(live):
+                c = int(crc[i])
+                for b in buf[int(s[i]) + j:int(s[i]) + int(length[i])].tolist():
+                    c = ((c << 8) & m) ^ tab[((c >> k) ^ b) & 0xFF]
+                crc[i] = c
+            break
         c = crc[:live]
         crc[:live] = ((c << np.uint32(8)) & mask) ^ table[((c >> sh) ^ buf[s[:live] + j]) & np.uint32(0xFF)]
+        j += 1
     out = np.zeros(s.size, np.uint32)
     out[order] = crc
     return out

@@ -17,7 +17,7 @@ SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "hop.hip", "md5.hip", "c
                                             "stream_plan.cpp", "resample_plan.cpp",
                                             "export_plan.cpp", "mel_plan.cpp", "pipeline.cpp", "seq_planner.cpp",
                                             "md5_host.cpp", "export_host.cpp", "mel_host.cpp", "abi.cpp")]
-HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "device_common.h", "launch.h", "dispatch.h",
+HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "crc16_math.h", "device_common.h", "launch.h", "dispatch.h",
                                            "stream_plan.h", "resample_plan.h", "export_plan.h", "mel_plan.h",
                                            "export_tile.h", "mix_tile.h", "mel_tile.h", "batch.h", "md5.hpp")]
 # the decode kernels' headers (decode.inc includes csrc/decode/*.h): dependencies of the decode_k* units only

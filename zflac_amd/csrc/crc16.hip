@@ -9,52 +9,12 @@
 // xor CRC(B): each lane hashes a contiguous 1/64 of the frame (whole aligned dwords,
 // slice-by-4 tables in LDS), multiplies its remainder by x^(8 * bytes after its piece) and
 // the wave xor-reduces. HBM-bound: each frame byte is read once.
+#include "crc16_math.h"
 #include "device_common.h"
 #include "launch.h"
 
 namespace zflac {
 namespace {
-
-constexpr uint32_t CRC16_P = 0x18005;  // x^16 + x^15 + x^2 + 1
-
-struct Crc16Tabs {
-    uint16_t t[4][256];  // t[k][v] = v(x) * x^(8k + 16) mod P
-};
-constexpr Crc16Tabs make_crc16_tabs() {
-    Crc16Tabs r{};
-    for (uint32_t v = 0; v < 256; v++) {
-        uint32_t c = v << 8;
-        for (int i = 0; i < 8; i++) c = (c & 0x8000) ? ((c << 1) ^ CRC16_P) : (c << 1);
-        r.t[0][v] = (uint16_t)c;
-    }
-    for (int k = 1; k < 4; k++)
-        for (uint32_t v = 0; v < 256; v++) {
-            const uint32_t c = r.t[k - 1][v];  // one more zero byte
-            r.t[k][v] = (uint16_t)(r.t[0][c >> 8] ^ ((c << 8) & 0xFFFF));
-        }
-    return r;
-}
-
-// a(x) * b(x) mod P for 16-bit remainders (Horner over b's bits, most significant first)
-__host__ __device__ constexpr uint32_t crc16_mulmod(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r <<= 1;
-        if (r & 0x10000) r ^= CRC16_P;
-        if ((b >> i) & 1) r ^= a;
-    }
-    return r;
-}
-
-struct Crc16Pow {
-    uint16_t p[40];  // p[k] = x^(8 * 2^k) mod P
-};
-constexpr Crc16Pow make_crc16_pow() {
-    Crc16Pow r{};
-    r.p[0] = 0x100;  // x^8
-    for (int k = 1; k < 40; k++) r.p[k] = (uint16_t)crc16_mulmod(r.p[k - 1], r.p[k - 1]);
-    return r;
-}
 
 static __constant__ Crc16Tabs CRC16T = make_crc16_tabs();
 static __constant__ Crc16Pow CRC16POW = make_crc16_pow();
