@@ -668,6 +668,108 @@ typedef struct zflac_mel_cmvn_desc {
 } zflac_mel_cmvn_desc;
 int zflac_hip_mel_cmvn(zflac_mel *m, const zflac_mel_cmvn_desc *c, void *stream);
 
+/* Cepstra and dynamic features behind the log-mel features: a projection of every frame's bins by
+ * a matrix (MFCC: a DCT with the lifter folded in; kernel k_mel_dct), the normalisation of
+ * zflac_hip_mel_cmvn over the projected features, and Kaldi's add-deltas (kernel k_mel_delta). A
+ * cepstra plan holds what the kernels read on the device: the matrix T (n_out x n_in f32,
+ * row-major) and the delta scales. The tensors are those of the mel plans: rows x C x frames
+ * (ZFLAC_MEL_BINS_FIRST) or rows x frames x C (ZFLAC_MEL_FRAMES_FIRST) elements, contiguous.
+ *
+ * matrix == NULL: no projection, the plan computes deltas only; n_out must equal n_in and in_dtype
+ * out_dtype. delta_order == 0: the plan only projects. A plan with neither is refused.
+ *
+ * Delta scales (Kaldi's DeltaFeatures): s_0 = [1], s_o = s_{o-1} convolved with
+ * [j / sum_{|i| <= W} i^2, j = -W..W], W = delta_window; s_o has 2 o W + 1 taps, j = -oW..oW. They
+ * are built in double and rounded to f32 once. Order 1, W = 2: [-2, -1, 0, 1, 2] / 10. Order 2,
+ * W = 2: [4, 4, 1, -4, -10, -4, 1, 4, 4] / 100. zflac_hip_cepstra_delta_scales copies the taps of
+ * one order (0..delta_order) to out and returns their count, or -ZFLAC_E_INVALID_ARGUMENT for a
+ * NULL plan or out, an order above the plan's, or cap below the count.
+ *
+ * zflac_hip_cepstra_create checks, in this order, before the device is touched
+ * (ZFLAC_E_INVALID_ARGUMENT): NULL d or out; size; in_dtype, out_dtype (ZFLAC_EXPORT_F32 / _F16 /
+ * _BF16); layout; delta_order > 3; n_in, then n_out (1..256 each); delta_window (1..5 when
+ * delta_order > 0, else 0); reserved; with matrix == NULL: n_out != n_in, in_dtype != out_dtype,
+ * delta_order == 0; with a matrix: every value finite. Then the device (ZFLAC_E_DEVICE).
+ *
+ * The three run calls take the caller's stream with the semantics of zflac_hip_mel_cmvn: nothing is
+ * staged from the host, rows == 0 is ZFLAC_OK with nothing done, and a refused call enqueues
+ * nothing. No kernel uses atomics: a run repeats bit for bit, and a frame's bits do not depend on
+ * the row count, on the row's position, on where the frame sits in the call's window (but see the
+ * deltas' edges) or on the alignment of the tensors.
+ *
+ * zflac_hip_cepstra_project: src_device is rows x n_in x frames of in_dtype, dst_device rows x
+ * n_out x frames of out_dtype, both in the plan's layout. With l[m] the stored bin m of a frame,
+ *   out[k] = conv_out( sum_{m < n_in} T[k][m] * widen(l[m]) )
+ * in f32: acc = 0, then acc = fma(T[k][m], l[m], acc) for m = 0, 1, .. n_in - 1, the same in both
+ * layouts. Every frame handed over is computed; the call takes no lengths. A non-finite value
+ * stays in its frame.
+ * Refused (ZFLAC_E_INVALID_ARGUMENT), in this order: NULL p or r; size; reserved; a plan without a
+ * matrix; NULL src_device, then dst_device; src_device == dst_device; src_device not aligned to
+ * in_dtype's size, dst_device to out_dtype's; frames == 0; rows * n_in * frames * in_dtype's size,
+ * then rows * n_out * frames * out_dtype's size, not fitting 63 bits.
+ *
+ * zflac_hip_cepstra_cmvn is zflac_hip_mel_cmvn with n_out for the bin count and the plan's
+ * out_dtype and layout: the same descriptor, the same kernel launch, the same bits and the same
+ * refusals in the same order. Kaldi normalises cepstra before it appends deltas.
+ *
+ * zflac_hip_cepstra_deltas: src_device is rows x C x frames, dst_device rows x (delta_order + 1) C
+ * x frames, C = n_out, both of out_dtype in the plan's layout. Feature block o (features o C ..
+ * o C + C - 1) is the o-th derivative, block 0 the input; frames first, a frame's (delta_order + 1) C
+ * values are contiguous in Kaldi's order: base, delta, delta-delta. F_i = min(valid_device[i],
+ * frames), or frames when valid_device is NULL. For t < F_i
+ *   out_o[c][t] = conv( sum_{j = -oW..oW} s_o[j] * widen(x[c][clamp(t + j, 0, F_i - 1)]) )
+ * in f32: acc = 0, then acc = fma(s_o[j], x, acc) for j = -oW, .. oW, an order fixed by (o, W)
+ * alone. Block 0 is the exact copy. For t >= F_i every block holds conv(pad_value); nothing at or
+ * past F_i is read. This is Kaldi's ComputeDeltas: one pass over the base features with the index
+ * clamped, not the delta operator applied o times. It differs from
+ * torchaudio.functional.compute_deltas applied twice only within 2 W frames of a row's ends. As
+ * with CMVN, the edge frames depend on the frame window the caller hands over: the clamp is at the
+ * first frame of the call and at F_i.
+ * Refused (ZFLAC_E_INVALID_ARGUMENT), in this order: NULL p or r; size; reserved, then reserved2; a
+ * plan with delta_order == 0; NULL src_device, then dst_device; src_device == dst_device; either not aligned
+ * to out_dtype's size; frames == 0; rows * (delta_order + 1) * n_out * frames * out_dtype's size
+ * not fitting 63 bits; valid_device not 8-byte aligned; pad_value not finite.
+ *
+ * Not provided: Kaldi's use_energy / raw_energy (C0 is the DCT's row 0), dither, frame splicing
+ * and low-frame-rate stacking. */
+typedef struct zflac_cepstra zflac_cepstra;
+typedef struct zflac_cepstra_desc {
+    uint32_t size;                 /* sizeof(zflac_cepstra_desc): 24 on LP64 */
+    uint8_t  in_dtype, out_dtype, layout, delta_order;  /* ZFLAC_EXPORT_F32/_F16/_BF16 twice; ZFLAC_MEL_BINS_FIRST/_FRAMES_FIRST; 0..3 */
+    uint16_t n_in, n_out;          /* 1..256 each; matrix == NULL: n_out must equal n_in */
+    uint8_t  delta_window;         /* 1..5 when delta_order > 0, else 0 */
+    uint8_t  reserved[3];          /* 0 */
+    const float *matrix;           /* host, n_out x n_in row-major, every value finite; or NULL: no projection */
+} zflac_cepstra_desc;
+int zflac_hip_cepstra_create(const zflac_cepstra_desc *d, int device, zflac_cepstra **out);
+void zflac_hip_cepstra_destroy(zflac_cepstra *p);
+/* n_out * (delta_order + 1); 0 for NULL */
+uint32_t zflac_hip_cepstra_features(const zflac_cepstra *p);
+int zflac_hip_cepstra_delta_scales(const zflac_cepstra *p, uint32_t order, float *out, uint32_t cap);
+
+typedef struct zflac_cepstra_project_desc {
+    uint32_t size;             /* sizeof(zflac_cepstra_project_desc): 40 on LP64 */
+    uint32_t reserved;         /* must be 0 */
+    const void *src_device;    /* rows x n_in x frames of in_dtype, the plan's layout */
+    void *dst_device;          /* rows x n_out x frames of out_dtype, the plan's layout */
+    uint64_t rows, frames;
+} zflac_cepstra_project_desc;
+int zflac_hip_cepstra_project(zflac_cepstra *p, const zflac_cepstra_project_desc *r, void *stream);
+
+int zflac_hip_cepstra_cmvn(zflac_cepstra *p, const zflac_mel_cmvn_desc *c, void *stream);
+
+typedef struct zflac_cepstra_delta_desc {
+    uint32_t size;                 /* sizeof(zflac_cepstra_delta_desc): 56 on LP64 */
+    uint32_t reserved;             /* must be 0 */
+    const void *src_device;        /* rows x n_out x frames of out_dtype, the plan's layout */
+    void *dst_device;              /* rows x (delta_order + 1) n_out x frames of out_dtype */
+    uint64_t rows, frames;
+    const uint64_t *valid_device;  /* per row, valid frames; or NULL: frames */
+    float pad_value;               /* finite; stored in every block at frames >= F_i */
+    uint32_t reserved2;            /* must be 0 */
+} zflac_cepstra_delta_desc;
+int zflac_hip_cepstra_deltas(zflac_cepstra *p, const zflac_cepstra_delta_desc *r, void *stream);
+
 /* Flags for zflac_hip_batch_create */
 #define ZFLAC_FLAG_TIMING 1        /* record HIP events around each kernel */
 #define ZFLAC_FLAG_FORCE_SLOW 2    /* skip the parallel fast path (testing the sequential path) */
@@ -730,7 +832,10 @@ const char *zflac_hip_build_id(void);
  *    zflac_hip_batch_md5_stats, ZFLAC_MD5_K_*; ZFLAC_MEL_MATH_*, zflac_hip_mel_create_ex,
  *    zflac_hip_mel_math; zflac_mel_frame_desc, ZFLAC_FRAMING_*, ZFLAC_PAD_MIRROR,
  *    zflac_hip_mel_create_framed, zflac_hip_mel_plan_frames; zflac_mel_cmvn_desc, ZFLAC_CMVN_*,
- *    zflac_hip_mel_cmvn. */
+ *    zflac_hip_mel_cmvn; zflac_cepstra, zflac_cepstra_desc, zflac_hip_cepstra_create,
+ *    zflac_hip_cepstra_destroy, zflac_hip_cepstra_features, zflac_hip_cepstra_delta_scales,
+ *    zflac_cepstra_project_desc, zflac_hip_cepstra_project, zflac_hip_cepstra_cmvn,
+ *    zflac_cepstra_delta_desc, zflac_hip_cepstra_deltas. */
 #define ZFLAC_HIP_ABI_VERSION 5
 int zflac_hip_abi_version(void);
 

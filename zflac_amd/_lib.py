@@ -80,6 +80,24 @@ class zflac_mel_cmvn_desc(ctypes.Structure):
                 ("std_device", ctypes.c_void_p), ("eps", ctypes.c_float), ("pad_value", ctypes.c_float)]
 
 
+class zflac_cepstra_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("in_dtype", ctypes.c_uint8), ("out_dtype", ctypes.c_uint8),
+                ("layout", ctypes.c_uint8), ("delta_order", ctypes.c_uint8), ("n_in", ctypes.c_uint16),
+                ("n_out", ctypes.c_uint16), ("delta_window", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
+                ("matrix", ctypes.POINTER(ctypes.c_float))]
+
+
+class zflac_cepstra_project_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("src_device", ctypes.c_void_p),
+                ("dst_device", ctypes.c_void_p), ("rows", ctypes.c_uint64), ("frames", ctypes.c_uint64)]
+
+
+class zflac_cepstra_delta_desc(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("src_device", ctypes.c_void_p),
+                ("dst_device", ctypes.c_void_p), ("rows", ctypes.c_uint64), ("frames", ctypes.c_uint64),
+                ("valid_device", ctypes.c_void_p), ("pad_value", ctypes.c_float), ("reserved2", ctypes.c_uint32)]
+
+
 # every symbol include/zflac_hip.h declares, with (restype, argtypes)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -129,6 +147,13 @@ SIGNATURES = {
                                                    ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(_P)]),
     "zflac_hip_mel_plan_frames": (ctypes.c_uint64, [_P, ctypes.c_uint64]),
     "zflac_hip_mel_cmvn": (ctypes.c_int, [_P, ctypes.POINTER(zflac_mel_cmvn_desc), _P]),
+    "zflac_hip_cepstra_create": (ctypes.c_int, [ctypes.POINTER(zflac_cepstra_desc), ctypes.c_int, ctypes.POINTER(_P)]),
+    "zflac_hip_cepstra_destroy": (None, [_P]),
+    "zflac_hip_cepstra_features": (ctypes.c_uint32, [_P]),
+    "zflac_hip_cepstra_delta_scales": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_uint32]),
+    "zflac_hip_cepstra_project": (ctypes.c_int, [_P, ctypes.POINTER(zflac_cepstra_project_desc), _P]),
+    "zflac_hip_cepstra_cmvn": (ctypes.c_int, [_P, ctypes.POINTER(zflac_mel_cmvn_desc), _P]),
+    "zflac_hip_cepstra_deltas": (ctypes.c_int, [_P, ctypes.POINTER(zflac_cepstra_delta_desc), _P]),
     "zflac_hip_batch_decode_buckets": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32),
                                                       ctypes.POINTER(ctypes.c_uint32)]),
     "zflac_hip_batch_front": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

@@ -13,12 +13,12 @@ LIB = os.path.join(HERE, "libzflac_hip.so")
 SOURCES = [os.path.join(CSRC, f"decode_k{k}_{lay}{mix}.hip") for k in (1, 2, 0) for lay in ("stereo", "mono", "multi")
            for mix in ("", "_mix")]
 SOURCES += [os.path.join(CSRC, n) for n in ("scan.hip", "hop.hip", "md5.hip", "crc16.hip", "walk_wave.hip", "export.hip",
-                                            "resample.hip", "mel.hip", "mel_bf16.hip", "mel_cmvn.hip",
-                                            "stream_plan.cpp", "resample_plan.cpp",
+                                            "resample.hip", "mel.hip", "mel_bf16.hip", "mel_cmvn.hip", "cepstra.hip",
+                                            "stream_plan.cpp", "resample_plan.cpp", "cepstra_plan.cpp",
                                             "export_plan.cpp", "mel_plan.cpp", "pipeline.cpp", "seq_planner.cpp",
-                                            "md5_host.cpp", "export_host.cpp", "mel_host.cpp", "abi.cpp")]
+                                            "md5_host.cpp", "export_host.cpp", "mel_host.cpp", "cepstra_host.cpp", "abi.cpp")]
 HEADERS = [os.path.join(CSRC, n) for n in ("common.h", "frame_header.h", "crc16_math.h", "device_common.h", "launch.h", "dispatch.h",
-                                           "stream_plan.h", "resample_plan.h", "export_plan.h", "mel_plan.h",
+                                           "stream_plan.h", "resample_plan.h", "export_plan.h", "mel_plan.h", "cepstra_plan.h",
                                            "export_tile.h", "mix_tile.h", "mel_tile.h", "batch.h", "md5.hpp")]
 # the decode kernels' headers (decode.inc includes csrc/decode/*.h): dependencies of the decode_k* units only
 DECODE_HEADERS = [os.path.join(CSRC, "decode.inc")] + sorted(

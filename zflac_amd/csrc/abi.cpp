@@ -266,6 +266,28 @@ uint64_t zflac_hip_mel_frames(uint64_t n_samples, uint32_t n_fft, uint32_t hop, 
 
 void zflac_hip_mel_destroy(zflac_mel* m) { mel_destroy(m); }
 
+int zflac_hip_cepstra_create(const zflac_cepstra_desc* d, int device, zflac_cepstra** out) {
+    return cepstra_create(d, device, out);
+}
+
+void zflac_hip_cepstra_destroy(zflac_cepstra* p) { cepstra_destroy(p); }
+
+uint32_t zflac_hip_cepstra_features(const zflac_cepstra* p) { return cepstra_features(p); }
+
+int zflac_hip_cepstra_delta_scales(const zflac_cepstra* p, uint32_t order, float* out, uint32_t cap) {
+    return cepstra_delta_scales_of(p, order, out, cap);
+}
+
+int zflac_hip_cepstra_project(zflac_cepstra* p, const zflac_cepstra_project_desc* r, void* stream) {
+    return cepstra_project(p, r, stream);
+}
+
+int zflac_hip_cepstra_cmvn(zflac_cepstra* p, const zflac_mel_cmvn_desc* c, void* stream) { return cepstra_cmvn(p, c, stream); }
+
+int zflac_hip_cepstra_deltas(zflac_cepstra* p, const zflac_cepstra_delta_desc* r, void* stream) {
+    return cepstra_deltas(p, r, stream);
+}
+
 int zflac_hip_batch_resample_tables(zflac_batch* b, uint64_t* built, uint64_t* held_floats) {
     if (!b) return E_INVALID_ARGUMENT;
     if (built) *built = b->rs_built;

@@ -270,6 +270,17 @@ int mel_run(zflac_mel* m, const float* wave, uint64_t rows, uint64_t wave_frames
 int mel_run_ex(zflac_mel* m, const zflac_mel_run_desc* r, void* stream);
 void mel_destroy(zflac_mel* m);
 
+// cepstra_host.cpp
+// The cepstra plan (zflac_cepstra: the matrix and the delta scales on the device, the plan's own
+// stream) and its runs; the argument checks, the scales and the grids are cepstra_plan.h's.
+int cepstra_create(const zflac_cepstra_desc* d, int device, zflac_cepstra** out);
+uint32_t cepstra_features(const zflac_cepstra* c);
+int cepstra_delta_scales_of(const zflac_cepstra* c, uint32_t order, float* out, uint32_t cap);
+int cepstra_project(zflac_cepstra* c, const zflac_cepstra_project_desc* r, void* stream);
+int cepstra_cmvn(zflac_cepstra* c, const zflac_mel_cmvn_desc* d, void* stream);
+int cepstra_deltas(zflac_cepstra* c, const zflac_cepstra_delta_desc* r, void* stream);
+void cepstra_destroy(zflac_cepstra* c);
+
 }  // namespace zflac
 
 // ---------------------------------------------------------------------------------

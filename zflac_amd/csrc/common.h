@@ -464,4 +464,39 @@ struct MelCmvnArgs {
     float eps, pad_value;
 };
 
+// k_mel_dct (cepstra.hip): every frame's n_in bins projected by T to n_out features. A workgroup
+// pass takes CEPS_FRAMES frames of one row: the frames' bins go to LDS as f32, then a lane has one
+// frame and a wave CEPS_KB output rows at a time, T coming in by scalar loads.
+constexpr uint32_t CEPS_THREADS = 256;
+constexpr uint32_t CEPS_FRAMES = 64;  // frames of a row per workgroup pass: the lanes of a wave
+constexpr uint32_t CEPS_KB = 4;       // rows of T a wave carries at once
+
+struct MelDctArgs {
+    const void* src;   // rows x n_in x frames (or rows x frames x n_in) elements of the input dtype
+    void* dst;         // rows x n_out x frames (or rows x frames x n_out) elements of the output dtype
+    const float* T;    // n_out x n_in, row-major
+    uint64_t frames;
+    uint64_t tiles;    // passes per row: ceil(frames / CEPS_FRAMES)
+    uint64_t total;    // rows * tiles
+    uint32_t n_in, n_out;
+};
+
+// k_mel_delta (cepstra.hip): Kaldi's deltas of every (row, feature) over the row's valid frames.
+// Bins-first: a workgroup pass takes CEPS_THREADS frames of one (row, feature). Frames-first: a
+// pass takes CEPS_THREADS / C frames of one row, the features on the lanes (as k_mel_cmvn).
+constexpr uint32_t CEPS_MAX_ORDER = 3;
+constexpr uint32_t CEPS_MAX_WINDOW = 5;
+
+struct MelDeltaArgs {
+    const void* src;        // rows x C x frames (or rows x frames x C) elements of the dtype
+    void* dst;              // rows x (order + 1) C x frames (or rows x frames x (order + 1) C)
+    const float* scales;    // the taps of order 1, then 2, .. (2 o W + 1 each)
+    const uint64_t* valid;  // per row, clamped to frames; NULL = frames
+    uint64_t frames;
+    uint64_t tiles;         // passes per (row, feature) (bins first) or per row (frames first)
+    uint64_t total;         // passes
+    uint32_t C, order, window;
+    float pad_value;
+};
+
 }  // namespace zflac

@@ -74,4 +74,8 @@ hipError_t launch_mel_split(int dtype, int layout, uint32_t m_tiles, uint32_t te
 // mel_cmvn.hip: k_mel_cmvn over a.total passes, at most 2^31 - 1 workgroups
 hipError_t launch_mel_cmvn(int dtype, int layout, const MelCmvnArgs& a, hipStream_t st);
 
+// cepstra.hip: k_mel_dct and k_mel_delta over a.total passes, at most 2^31 - 1 workgroups
+hipError_t launch_mel_dct(int in_dtype, int out_dtype, int layout, const MelDctArgs& a, hipStream_t st);
+hipError_t launch_mel_delta(int dtype, int layout, const MelDeltaArgs& a, hipStream_t st);
+
 }  // namespace zflac

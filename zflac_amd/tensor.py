@@ -371,6 +371,53 @@ def kaldi_mel_filters(sample_rate, n_fft, n_mels, low_freq=20.0, high_freq=0.0):
     return out
 
 
+def dct_matrix(n_ceps, n_mels, norm="ortho", lifter=0.0):
+    """The DCT-II rows that take n_mels log-mel bins to n_ceps cepstra -> numpy float32
+    [n_ceps, n_mels]. norm="ortho" (Kaldi, torchaudio's and librosa's default): row 0 is
+    sqrt(1 / M), row k sqrt(2 / M) cos(pi k (m + 1/2) / M), M = n_mels; norm=None: 2 cos(...) for
+    every row (torchaudio's create_dct(norm=None)). lifter Q > 0 folds Kaldi's cepstral lifter
+    1 + (Q / 2) sin(pi k / Q) into row k (0: none). Computed in float64 and rounded once."""
+    import math as _math
+
+    import numpy as np
+
+    n_ceps, n_mels, lifter = int(n_ceps), int(n_mels), float(lifter)
+    if not (1 <= n_mels <= 256 and 1 <= n_ceps <= n_mels):
+        raise ValueError("1 <= n_ceps <= n_mels <= 256")
+    if norm not in ("ortho", None):
+        raise ValueError("norm is 'ortho' or None")
+    if not (_math.isfinite(lifter) and lifter >= 0.0):
+        raise ValueError("lifter finite and >= 0")
+    k = np.arange(n_ceps, dtype=np.float64)[:, None]
+    m = np.arange(n_mels, dtype=np.float64)[None, :]
+    d = np.cos(np.pi * k * (m + 0.5) / n_mels)
+    if norm == "ortho":
+        d *= np.sqrt(2.0 / n_mels)
+        d[0] = np.sqrt(1.0 / n_mels)
+    else:
+        d *= 2.0
+    if lifter > 0.0:
+        d *= 1.0 + 0.5 * lifter * np.sin(np.pi * k / lifter)
+    return d.astype(np.float32)
+
+
+def delta_scales(order, window):
+    """Kaldi's delta taps (DeltaFeatures) -> numpy float64 [2 order window + 1], tap j = -order W ..
+    order W: s_0 = [1], s_o = s_{o-1} convolved with [j / sum_{|i| <= W} i^2, j = -W..W]. Order 1,
+    W = 2: [-2, -1, 0, 1, 2] / 10; order 2: [4, 4, 1, -4, -10, -4, 1, 4, 4] / 100."""
+    import numpy as np
+
+    order, window = int(order), int(window)
+    if not (0 <= order <= 3 and 1 <= window <= 5):
+        raise ValueError("0 <= order <= 3, 1 <= window <= 5")
+    j = np.arange(-window, window + 1, dtype=np.float64)
+    step = j / np.sum(j * j)
+    s = np.ones(1, dtype=np.float64)
+    for _ in range(order):
+        s = np.convolve(s, step)
+    return s
+
+
 _MEL_SCALES = {"power": _lib.MEL_POWER, "log10": _lib.MEL_LOG10, "ln": _lib.MEL_LN}
 _MEL_LAYOUTS = {"bins_first": _lib.MEL_BINS_FIRST, "frames_first": _lib.MEL_FRAMES_FIRST}
 _MEL_PADS = {"zeros": _lib.PAD_ZEROS, "reflect": _lib.PAD_REFLECT, "mirror": _lib.PAD_MIRROR}
@@ -426,7 +473,20 @@ class MelSpectrogram:
     row's feature_lengths valid frames (zflac_hip_mel_cmvn, k_mel_cmvn): (x - mean) / (std + cmvn_eps),
     std with cmvn_ddof 0 or 1, frames past the valid ones set to cmvn_pad. The statistics of the
     last call are mel.last_mean and mel.last_std ([B, (C,) n_bins] float32).
-    Not provided: dither, use_energy / raw_energy, VTLN, pre-emphasis over the whole waveform.
+
+    Cepstra and dynamic features (a cepstra plan of the library beside the mel plan; without these
+    arguments a call is exactly what it was). mfcc: None, a cepstra count (the matrix is
+    dct_matrix(mfcc, n_bins, dct_norm, lifter)) or an array [n_out, n_bins]: every frame's bins are
+    projected by it (zflac_hip_cepstra_project, k_mel_dct). The mel plan then writes float32
+    whatever `dtype` is, so the projection reads unrounded log-mels. deltas: None or (order 1..3,
+    window 1..5): Kaldi's add-deltas (zflac_hip_cepstra_deltas, k_mel_delta) appends the 1st ..
+    order-th derivatives, block o at features o C .. o C + C - 1, over the row's feature_lengths
+    valid frames (the clamp is at the first frame of the call and at the last valid one); frames
+    past them hold cmvn_pad. A call enqueues, in order: the mel run, the projection, cmvn over
+    the base features (the cepstra if projected, else the bins; last_mean / last_std have that
+    many columns), the deltas. dtype is the final tensor's and mel.n_features its feature count.
+    Not provided: dither, use_energy / raw_energy, VTLN, pre-emphasis over the whole waveform,
+    frame splicing and low-frame-rate stacking.
     The object owns a plan of the library: close() it, or use it in `with`."""
 
     @classmethod
@@ -442,7 +502,8 @@ class MelSpectrogram:
     @classmethod
     def kaldi_fbank(cls, sample_rate=16000, num_mel_bins=80, frame_length_ms=25.0, frame_shift_ms=10.0, snip_edges=True,
                     preemphasis=0.97, remove_dc=True, window="povey", low_freq=20.0, high_freq=0.0, math="f32",
-                    dtype=torch.float32, cmvn=None, device=0, **cmvn_kw):
+                    dtype=torch.float32, cmvn=None, device=0, mfcc=None, lifter=0.0, dct_norm="ortho", deltas=None,
+                    **cmvn_kw):
         """Kaldi's compute-fbank-feats (kaldifeat, torchaudio.compliance.kaldi.fbank, lhotse) for
         waveforms in [-1, 1): frames of frame_length_ms every frame_shift_ms in the next power-of-two
         DFT, the samples scaled by 32768, DC removal, pre-emphasis and the window per frame,
@@ -459,18 +520,45 @@ class MelSpectrogram:
                    floor=2.0 ** -23, center=False, dtype=dtype, layout="frames_first", device=device,
                    pad="zeros" if snip_edges else "mirror", math=math, win_length=nw,
                    framing="snip" if snip_edges else "kaldi_center", remove_dc=remove_dc, preemphasis=preemphasis,
-                   sample_scale=32768.0, cmvn=cmvn, **cmvn_kw)
+                   sample_scale=32768.0, cmvn=cmvn, mfcc=mfcc, lifter=lifter, dct_norm=dct_norm, deltas=deltas,
+                   **cmvn_kw)
+
+    @classmethod
+    def kaldi_mfcc(cls, sample_rate=16000, num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, use_energy=False,
+                   **fbank_kw):
+        """Kaldi's compute-mfcc-feats (kaldifeat's Mfcc, torchaudio.compliance.kaldi.mfcc) with
+        use_energy=False: kaldi_fbank(sample_rate, num_mel_bins, **fbank_kw), then the orthonormal
+        DCT to num_ceps cepstra with the lifter 1 + (Q / 2) sin(pi k / Q), Q = cepstral_lifter
+        (0: none), [B, (C,) frames, num_ceps]. cmvn= normalises the cepstra; deltas=(2, 2) appends
+        add-deltas' columns behind that. use_energy / raw_energy (C0 replaced by the frame's log
+        energy) is not provided: C0 is the DCT's row 0."""
+        if use_energy:
+            raise ValueError("use_energy=True is not provided: C0 is the DCT's row 0, not the frame's log energy")
+        for k in ("mfcc", "lifter", "dct_norm"):
+            if k in fbank_kw:
+                raise TypeError(f"kaldi_mfcc() sets {k}; use num_ceps and cepstral_lifter")
+        return cls.kaldi_fbank(sample_rate, num_mel_bins, mfcc=int(num_ceps), lifter=cepstral_lifter, **fbank_kw)
 
     def __init__(self, sample_rate, n_fft=400, hop=160, n_mels=80, window="hann", filters=None, scale="log10",
                  floor=1e-10, center=True, dtype=torch.float32, layout="bins_first", device=0, pad="zeros",
                  normalize=None, reflect_at="length", math="f32", win_length=None, framing="stft", remove_dc=False,
-                 preemphasis=0.0, sample_scale=1.0, cmvn=None, cmvn_eps=1e-5, cmvn_ddof=0, cmvn_pad=0.0, **filter_kw):
+                 preemphasis=0.0, sample_scale=1.0, cmvn=None, cmvn_eps=1e-5, cmvn_ddof=0, cmvn_pad=0.0, mfcc=None,
+                 lifter=0.0, dct_norm="ortho", deltas=None, **filter_kw):
         import math as _math
 
         import numpy as np
 
+        self._h = self._c = None
         if math not in _MEL_MATHS:
             raise ValueError("math is 'f32', 'bf16x6' or 'bf16x3'")
+        if deltas is not None:
+            try:
+                deltas = tuple(int(v) for v in deltas)
+            except TypeError:
+                raise ValueError("deltas is None or (order, window)") from None
+            if len(deltas) != 2 or not (1 <= deltas[0] <= 3 and 1 <= deltas[1] <= 5):
+                raise ValueError("deltas is None or (order 1..3, window 1..5)")
+        self.deltas = deltas
         check_single_runtime()
         if pad not in _MEL_PADS:
             raise ValueError("pad is 'zeros', 'reflect' or 'mirror'")
@@ -547,7 +635,35 @@ class MelSpectrogram:
         self.window, self.filters = w, fb
         self.win_length, self.framing, self.remove_dc = nw, framing, bool(remove_dc)
         self.preemphasis, self.sample_scale = preemphasis, sample_scale
+        if mfcc is None:
+            if lifter != 0.0:
+                raise ValueError("lifter needs mfcc")
+            T = None
+        elif isinstance(mfcc, (int, np.integer)) and not isinstance(mfcc, bool):
+            T = dct_matrix(mfcc, self.n_bins, dct_norm, lifter)
+        else:
+            if lifter != 0.0:
+                raise ValueError("with a matrix for mfcc, fold the lifter into it")
+            T = np.ascontiguousarray(mfcc.detach().cpu().numpy() if isinstance(mfcc, torch.Tensor) else mfcc, dtype=np.float32)
+            if T.ndim != 2 or T.shape[1] != self.n_bins or not 1 <= T.shape[0] <= 256:
+                raise ValueError(f"mfcc has shape {T.shape}, expected (1..256, {self.n_bins})")
+            if not np.isfinite(T).all():
+                raise ValueError("mfcc: every value finite")
+        self.dct = T
+        self.n_base = self.n_bins if T is None else int(T.shape[0])  # what cmvn normalises and the deltas extend
+        self.n_features = self.n_base * (1 + (deltas[0] if deltas else 0))
+        mel_dtype = dtype if T is None else torch.float32  # the projection reads unrounded log-mels
         self._L = _lib.load()
+        if T is not None or deltas:
+            cd = _lib.zflac_cepstra_desc(ctypes.sizeof(_lib.zflac_cepstra_desc), _DTYPES[mel_dtype], _DTYPES[dtype],
+                                         _MEL_LAYOUTS[layout], deltas[0] if deltas else 0, self.n_bins, self.n_base,
+                                         deltas[1] if deltas else 0, (ctypes.c_uint8 * 3)(),
+                                         None if T is None else T.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+            c = ctypes.c_void_p()
+            errors.check(self._L.zflac_hip_cepstra_create(ctypes.byref(cd), self.device, ctypes.byref(c)), "cepstra_create")
+            self._c = c
+        self._mel_dtype = mel_dtype
+        dtype = mel_dtype  # of the mel plan below; self.dtype is the final tensor's
         desc = _lib.zflac_mel_desc(ctypes.sizeof(_lib.zflac_mel_desc), _DTYPES[dtype], _MEL_LAYOUTS[layout],
                                    _MEL_SCALES[scale], int(self.center), n_fft, hop, self.n_bins, 0, self.floor,
                                    w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
@@ -610,7 +726,7 @@ class MelSpectrogram:
         if frames < 1:
             raise ValueError("frames >= 1")
         lead = tuple(x.shape[:-1])
-        shape = lead + ((self.n_bins, frames) if self.layout == "bins_first" else (frames, self.n_bins))
+        shape = lead + ((self.n_features, frames) if self.layout == "bins_first" else (frames, self.n_features))
         if out is None:
             out = torch.empty(shape, dtype=self.dtype, device=dev)
         else:
@@ -642,11 +758,15 @@ class MelSpectrogram:
             stream = torch.cuda.current_stream(dev)
         if not stream.cuda_stream:
             stream.synchronize()  # the null stream has no handle: the plan's own stream, complete on return
+        feat = out  # what the mel run writes: the result, or the bins a cepstra plan goes on from
+        if self._c is not None:
+            feat = torch.empty(lead + ((self.n_bins, frames) if self.layout == "bins_first" else (frames, self.n_bins)),
+                               dtype=self._mel_dtype, device=dev)
         if not ex:
-            rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, out.data_ptr(),
-                                           out.numel() * out.element_size(), stream.cuda_stream or None)
+            rc = self._L.zflac_hip_mel_run(self._h, x.data_ptr(), rows, T, T, first_frame, frames, feat.data_ptr(),
+                                           feat.numel() * feat.element_size(), stream.cuda_stream or None)
             errors.check(rc, "mel_run")
-            self._cmvn(out, lead, rows, frames, feature_lengths, stream)
+            self._finish(feat, out, lead, rows, frames, feature_lengths, stream)
             return out, feature_lengths
         per_row = None
         if self.reflect_at == "length":  # one length per row of the launch: [B, C, T] has C rows per entry
@@ -655,28 +775,61 @@ class MelSpectrogram:
         d = _lib.zflac_mel_run_desc(ctypes.sizeof(_lib.zflac_mel_run_desc), _MEL_PADS[self.pad],
                                     _lib.NORM_NONE if self.normalize is None else _lib.NORM_ROW_MAX, 0, x.data_ptr(), rows,
                                     T, T, None if per_row is None else per_row.data_ptr(), first_frame, frames,
-                                    out.data_ptr(), out.numel() * out.element_size(), row_max.data_ptr(), rng, add, mul, 0)
+                                    feat.data_ptr(), feat.numel() * feat.element_size(), row_max.data_ptr(), rng, add, mul, 0)
         rc = self._L.zflac_hip_mel_run_ex(self._h, ctypes.byref(d), stream.cuda_stream or None)
         errors.check(rc, "mel_run_ex")
         self._keep = per_row  # read by the launch: alive until the next call, and not reused before `stream` is past it
         for t in (per_row, row_max):
             if t is not None and stream.cuda_stream:
                 t.record_stream(stream)
-        self._cmvn(out, lead, rows, frames, feature_lengths, stream)
+        self._finish(feat, out, lead, rows, frames, feature_lengths, stream)
         return (out, feature_lengths, row_max) if return_row_max else (out, feature_lengths)
 
-    def _cmvn(self, out, lead, rows, frames, feature_lengths, stream):
-        """zflac_hip_mel_cmvn over the features just enqueued, feature_lengths as the valid frames."""
+    def _finish(self, feat, out, lead, rows, frames, feature_lengths, stream):
+        """What follows the mel run that wrote `feat`. Without a cepstra plan feat is out and this is
+        the cmvn step. With one: the projection, cmvn over the base features, the deltas, ending in out."""
+        if self._c is None:
+            self._cmvn(out, lead, rows, frames, feature_lengths, stream)
+            return
+        st = stream.cuda_stream or None
+        base, temps = feat, [feat]
+        if self.dct is not None:
+            base = out
+            if self.deltas:
+                base = torch.empty(feat.shape[:-2] + ((self.n_base, frames) if self.layout == "bins_first" else
+                                                      (frames, self.n_base)), dtype=self.dtype, device=out.device)
+                temps.append(base)
+            d = _lib.zflac_cepstra_project_desc(ctypes.sizeof(_lib.zflac_cepstra_project_desc), 0, feat.data_ptr(),
+                                                base.data_ptr(), rows, frames)
+            errors.check(self._L.zflac_hip_cepstra_project(self._c, ctypes.byref(d), st), "cepstra_project")
+        self._cmvn(base, lead, rows, frames, feature_lengths, stream, projected=self.dct is not None)
+        if self.deltas:
+            valid = feature_lengths.repeat_interleave(rows // int(feature_lengths.shape[0])).contiguous()
+            d = _lib.zflac_cepstra_delta_desc(ctypes.sizeof(_lib.zflac_cepstra_delta_desc), 0, base.data_ptr(),
+                                              out.data_ptr(), rows, frames, valid.data_ptr(), self.cmvn_pad, 0)
+            errors.check(self._L.zflac_hip_cepstra_deltas(self._c, ctypes.byref(d), st), "cepstra_deltas")
+            temps.append(valid)
+        self._keep_ceps = temps  # as _keep: read by the launches
+        for t in temps:
+            if stream.cuda_stream:
+                t.record_stream(stream)
+
+    def _cmvn(self, out, lead, rows, frames, feature_lengths, stream, projected=False):
+        """zflac_hip_mel_cmvn (zflac_hip_cepstra_cmvn over projected features) over the features just
+        enqueued, feature_lengths as the valid frames."""
         if self.cmvn is None:
             return
         dev = out.device
         valid = feature_lengths.repeat_interleave(rows // int(feature_lengths.shape[0])).contiguous()
-        mean = torch.empty(lead + (self.n_bins,), dtype=torch.float32, device=dev)
+        mean = torch.empty(lead + (self.n_base if projected else self.n_bins,), dtype=torch.float32, device=dev)
         std = torch.empty_like(mean)
         d = _lib.zflac_mel_cmvn_desc(ctypes.sizeof(_lib.zflac_mel_cmvn_desc), _MEL_CMVN[self.cmvn], self.cmvn_ddof, 0,
                                      out.data_ptr(), rows, frames, valid.data_ptr(), mean.data_ptr(), std.data_ptr(),
                                      self.cmvn_eps, self.cmvn_pad)
-        errors.check(self._L.zflac_hip_mel_cmvn(self._h, ctypes.byref(d), stream.cuda_stream or None), "mel_cmvn")
+        if projected:
+            errors.check(self._L.zflac_hip_cepstra_cmvn(self._c, ctypes.byref(d), stream.cuda_stream or None), "cepstra_cmvn")
+        else:
+            errors.check(self._L.zflac_hip_mel_cmvn(self._h, ctypes.byref(d), stream.cuda_stream or None), "mel_cmvn")
         self._keep_cmvn = valid  # as _keep: read by the launch
         for t in (valid, mean, std):
             if stream.cuda_stream:
@@ -687,6 +840,9 @@ class MelSpectrogram:
         if getattr(self, "_h", None) is not None:
             self._L.zflac_hip_mel_destroy(self._h)  # waits for the device
             self._h = None
+        if getattr(self, "_c", None) is not None:
+            self._L.zflac_hip_cepstra_destroy(self._c)
+            self._c = None
 
     def __enter__(self):
         return self
