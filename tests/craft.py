@@ -214,6 +214,21 @@ def _utf8(n: int) -> list:
         lead, cap = (lead >> 1) | 0x80, cap >> 1
 
 
+RATE_TABLE = {1: 88200, 2: 176400, 3: 192000, 4: 8000, 5: 16000, 6: 22050, 7: 24000, 8: 32000, 9: 44100, 10: 48000,
+              11: 96000}
+_BS_TABLE = {192: 1, **{576 << k: 2 + k for k in range(4)}, **{1 << k: k for k in range(8, 16)}}
+
+
+def _bs_code(bs: int, bs_field):
+    """(block-size code, the bytes of its field) of a frame of `bs` samples."""
+    if bs_field == "table" and bs in _BS_TABLE:
+        return _BS_TABLE[bs], []
+    if bs_field == 8 or bs_field == "table" and bs <= 256:
+        assert bs <= 256
+        return 6, [bs - 1]
+    return 7, [(bs - 1) >> 8, (bs - 1) & 0xFF]
+
+
 def _zigzag(r: np.ndarray) -> np.ndarray:
     r = np.asarray(r, dtype=np.int64)
     return np.where(r >= 0, r << 1, ((-r) << 1) - 1).astype(np.uint64)
@@ -349,33 +364,59 @@ def _write_sub(F: _Fields, sub: Sub, bs: int, bps: int, ubps: int, W: int):
 
 
 def write(channels: int, bps: int, bs: int, frames, assignment: str = "indep", rate: int = 44100,
-          bs_field: int | None = None) -> Crafted:
+          bs_field: int | str | None = None, *, rate_code: int | None = None, blocking: str = "fixed",
+          first_number: int = 0, block_sizes=None) -> Crafted:
     """`frames`: one list of `channels` Subs per frame, every frame `bs` samples (fixed blocking,
     frame numbers from 0). `assignment`: "indep", or for two channels "ls", "sr", "ms": the Subs
     are then the coded channels (left/side, side/right, mid/side). `bs_field`: 8 or 16, the
     width of the header's block-size field (default: 8 bits where the block size allows; a
-    block of 256 then puts an FF byte in front of the CRC-8)."""
+    block of 256 then puts an FF byte in front of the CRC-8), or "table": the codes 1..5 and
+    8..15 where a frame's block size is 192, 576 << k or 1 << k, a field of 8 or 16 bits elsewhere.
+
+    The other header forms (the defaults write what the writer always wrote):
+    `rate_code`: any of 0..14 (default 9 for 44,100 Hz, else 0); 1..11 want `rate` to be the
+    table's, 12 writes it in 8 bits (in Hz: what zflac reads, src/zflac.zig:369), 13 in 16 bits,
+    14 in tens of Hz in 16 bits. STREAMINFO holds `rate` itself.
+    `blocking`: "variable" writes 0xF9 and numbers every frame by its first sample.
+    `first_number`: the first frame's coded number (the frame number, or the first sample's).
+    `block_sizes`: the block size of every frame (default: `bs` each). STREAMINFO's minimum and
+    maximum are `bs` where every frame but the last has `bs` samples under fixed blocking, and
+    the frames' own extremes elsewhere."""
     assert 1 <= channels <= 8 and 4 <= bps <= 32 and 16 <= bs <= 65535
-    bs_field = bs_field or (8 if bs <= 256 else 16)
-    assert bs_field == 16 or bs <= 256
+    sizes_ = [bs] * len(frames) if block_sizes is None else [int(x) for x in block_sizes]
+    assert len(sizes_) == len(frames) and all(16 <= x <= 65535 for x in sizes_[:-1]) and 1 <= sizes_[-1] <= 65535
+    assert blocking in ("fixed", "variable")
+    if bs_field != "table":
+        bs_field = bs_field or (8 if max(sizes_) <= 256 else 16)
+        assert bs_field == 16 or max(sizes_) <= 256
+    rc = rate_code if rate_code is not None else (9 if rate == 44100 else 0)
+    assert 0 <= rc <= 14 and 0 < rate < 1 << 20
+    if 1 <= rc <= 11:
+        assert rate == RATE_TABLE[rc]
+    rate_bytes = {12: [rate], 13: [rate >> 8, rate & 0xFF], 14: [rate // 10 >> 8, rate // 10 & 0xFF]}.get(rc, [])
+    assert all(0 <= x < 256 for x in rate_bytes) and (rc != 14 or rate % 10 == 0)
     code = ASSIGN[assignment]
     assert code is None or channels == 2
     SB, W = widths(bps)
     F = _Fields()
     marks, pcm, layout = [], [], []
     max_order, mix = 0, False
+    number = first_number
     for f, subs in enumerate(frames):
         assert len(subs) == channels
-        hdr = [0xFF, 0xF8, (6 if bs_field == 8 else 7) << 4 | (9 if rate == 44100 else 0),
-               (channels - 1 if code is None else code) << 4 | _DEPTH_CODE.get(bps, 0) << 1] + _utf8(f)
-        hdr += [bs - 1] if bs_field == 8 else [(bs - 1) >> 8, (bs - 1) & 0xFF]
+        fbs = sizes_[f]
+        bcode, bs_bytes = _bs_code(fbs, bs_field)
+        hdr = [0xFF, 0xF8 if blocking == "fixed" else 0xF9, bcode << 4 | rc,
+               (channels - 1 if code is None else code) << 4 | _DEPTH_CODE.get(bps, 0) << 1] + _utf8(number)
+        hdr += bs_bytes + rate_bytes
+        number += 1 if blocking == "fixed" else fbs
         assert F.bits % 8 == 0
         start_byte = F.bits // 8
         F.add(hdr + [0], 8)
         chans, lays = [], []
         for c, sub in enumerate(subs):
             side = code is not None and c == (0 if code == 9 else 1)
-            vals, lay = _write_sub(F, sub, bs, bps, bps + (1 if side else 0), W)
+            vals, lay = _write_sub(F, sub, fbs, bps, bps + (1 if side else 0), W)
             chans.append(vals)
             lays.append(lay)
             if sub.kind in ("const", "verbatim"):
@@ -404,10 +445,12 @@ def write(channels: int, bps: int, bs: int, frames, assignment: str = "indep", r
     cont = ((pcm + (1 << (SB - 1))) & ((1 << SB) - 1)) - (1 << (SB - 1))  # as the container holds it
     nbytes = (bps + 7) // 8
     msg = cont.astype("<i8").view(np.uint8).reshape(-1, 8)[:, :nbytes]
-    total = bs * len(frames)
+    total = sum(sizes_)
     sizes = ends - starts
+    nominal = blocking == "fixed" and all(x == bs for x in sizes_[:-1]) and sizes_[-1] <= bs
+    min_bs, max_bs = (bs, bs) if nominal else (min(sizes_), max(sizes_))
     si = _Fields()
-    si.add([bs, bs, int(sizes.min()), int(sizes.max()), rate, channels - 1, bps - 1, total], [16, 16, 24, 24, 20, 3, 5, 36])
+    si.add([min_bs, max_bs, int(sizes.min()), int(sizes.max()), rate, channels - 1, bps - 1, total], [16, 16, 24, 24, 20, 3, 5, 36])
     digest = hashlib.md5(np.ascontiguousarray(msg).tobytes()).digest()
     meta = b"fLaC" + bytes([0x80, 0, 0, 34]) + si.pack()[0].tobytes() + digest
     base = len(meta) * 8

@@ -175,7 +175,7 @@ def padded(flac: bytes, k) -> bytes:
     d = bytearray(flac[:42])
     assert d[:4] == b"fLaC" and d[4] == 0x80
     d[4] = 0x00
-    return bytes(d) + bytes([0x81, 0, 0, k]) + bytes(k) + flac[42:]
+    return bytes(d) + bytes([0x81]) + k.to_bytes(3, "big") + bytes(k) + flac[42:]  # (a 24-bit length)
 
 
 def unknown_total(flac: bytes) -> bytes:

@@ -1,6 +1,7 @@
-// frame_header.h -- the exact frame-header parser (src/zflac.zig:343-407), its format tables
-// and the register CRC-8. Plain C++20 with no HIP header: the kernels include it through
-// device_common.h, the host planner (stream_plan.cpp) directly, so both sides run one parser.
+// frame_header.h -- the exact frame-header parser (src/zflac.zig:343-407), its format tables,
+// the register CRC-8, the candidate filter and the SWAR sync-code masks of the frame scan. Plain
+// C++20 with no HIP header: the kernels include it through device_common.h, the host planner
+// (stream_plan.cpp) and the scan probe (tests/c/scan_probe.cpp) directly, so both sides run one text.
 #pragma once
 #include <cstdint>
 
@@ -264,6 +265,50 @@ ZFLAC_HDI FrameHdr parse_frame_header_t(At&& at, uint64_t avail, uint32_t si_rat
         h.crc_ok = crc == at(idx);
     }
     return h;
+}
+
+// Filter for sync candidates: a well-formed header consistent with the stream's first
+// frame. Anything it rejects that zflac would still decode breaks the verified chain and
+// sends the stream to the sequential planner, so the filter affects speed only.
+ZFLAC_HDI bool candidate_ok(const FrameHdr& h, const StreamDesc& S) {
+    return h.err == 0 && !h.crc_eof && h.crc_ok && h.zero_bit == 0 && h.byte1 == S.byte1 &&
+           channels_count(h.chan_code) == S.nch && h.dcode == S.dcode && h.rate == S.rate_hz;
+}
+
+// ----------------------------------------------------------------------------------
+// frame sync codes in registers (k_scan, k_hop; on the host: tests/c/scan_probe.cpp)
+// ----------------------------------------------------------------------------------
+ZFLAC_HD inline uint32_t ff_mask(uint32_t d) { return ((d & 0x7F7F7F7Fu) + 0x01010101u) & d & 0x80808080u; }
+
+// Byte i = the byte after byte i of d (byte 0 of dn for i = 3): v_alignbyte on the device.
+ZFLAC_HDI uint32_t bytes_after(uint32_t d, uint32_t dn) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_alignbyte(dn, d, 1);
+#else
+    return (d >> 8) | (dn << 24);
+#endif
+}
+
+// Bit 7 of byte i set where byte i of d is 0xFF and the byte after it (byte i + 1, or the
+// first byte of dn for i = 3) is 0xF8 or 0xF9: a frame sync code (src/zflac.zig:351-352).
+// Exact per byte (no borrow between bytes).
+ZFLAC_HDI uint32_t sync_mask(uint32_t d, uint32_t dn) {
+    const uint32_t nxt = bytes_after(d, dn);
+    const uint32_t y = (nxt & 0xFEFEFEFEu) ^ 0xF8F8F8F8u;  // zero bytes: next is 0xF8 / 0xF9
+    const uint32_t zero = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
+    return ff_mask(d) & zero;
+}
+
+// Nonzero iff some byte i of d is 0xFF and the byte after it 0xF8 / 0xF9: the same test as
+// sync_mask, as an existence test only. Byte i of t is zero exactly at a sync code, and
+// (t - 0x01..01) & ~t & 0x80..80 is nonzero iff t has a zero byte (the borrows can mark a
+// byte above a zero one, never create a mark without one). ~5 VALU per dword against
+// sync_mask's ~10: k_scan runs it on every window and the exact masks only where it fires
+// (a sync code, or a 0xFF 0xF8|F9 pair in the coded bits: ~1 in 7 wave-windows of 1 KiB).
+ZFLAC_HDI uint32_t sync_any(uint32_t d, uint32_t dn) {
+    const uint32_t nxt = bytes_after(d, dn);
+    const uint32_t t = ~d | ((nxt & 0xFEFEFEFEu) ^ 0xF8F8F8F8u);
+    return (t - 0x01010101u) & ~t & 0x80808080u;
 }
 
 // The value of the header's coded number (read_coded_number, src/zflac.zig:203-214; header
